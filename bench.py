@@ -2,14 +2,16 @@
 """Headline benchmark: VQA samples/s, forward+backward+optimizer step of the MCAN encoder stack
 (d=512, L=6, B=64 per GPU, 100 regions x 20 tokens, bf16) -- BASELINE.json `metric`, configs[1].
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One process per GPU (RCCL = torch.distributed "nccl"), weak scaling (64 samples per GPU).
 A "step" is: forward -> loss -> backward -> gradient all-reduce -> Adam, on synthetic inputs
-already resident in HBM.  Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP
-events, live) and `cpu_baseline` (the oracle restatement timed on the host cores, N=1 only).
+already resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times
+--steps steps and prints it; --full adds further timing windows, `roofline` (dominant kernel, HIP
+events, live), `secondary` and `cpu_baseline` (the oracle restatement timed on the host cores, N=1 only)
+and `gradient_exchange` (N>1).
 """
 from __future__ import annotations
 
@@ -79,16 +81,29 @@ def parse():
                          "the last grouped weight-gradient launch, TrainStep(fuse_adam=True); with N > 1 the gradient exchange "
                          "stands between gradient and update and Adam is always separate)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary workloads (model, cross_modality, decoder_train, decode beam 1 / 3, m4c_decode) that the default "
+                    help="skip the secondary workloads (model, cross_modality, decoder_train, decode beam 1 / 3, m4c_decode) that a --full "
                          "single-GPU run of the headline workload appends under `secondary`")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher self-test (no GPU): start the ranks exactly as a real run would, bring up a gloo "
                          "process group, count the ranks with an all-reduce and print the JSON skeleton with `n_gpus` = "
                          "the group's world size and `value` null")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed windows of --steps steps: the first is the contract's measurement (`value`), the rest "
-                         "give median / min / max in extra keys")
-    return ap.parse_args()
+                         "give median / min / max in extra keys (default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else this benchmark measures: the repeated timing "
+                         "windows, the in-step rooflines, the secondary workloads and the CPU baseline (N = 1), the "
+                         "per-segment gradient-exchange timing (`gradient_exchange`, N > 1 or --rehearse-comm).  Off by "
+                         "default: a plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32; at most 48 MiB in all, a fixed sample of the larger arrays): for a training workload "
+                         "the loss, the updated fp32 parameters and Adam's first moment; for a decode workload its "
+                         "tokens and scores")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def gemm_launch_list(B, NV, NT, D, DFF, L, in_step=False):
@@ -447,7 +462,43 @@ def cpu_baseline(cfg, steps, thread_list):
             "cpus_available": avail}
 
 
-def m4c_decode_bench(args, device, world, rank, dist, B, seed):
+DUMP_BUDGET = 48 * 2 ** 20  # bytes: every file of --dump-outputs together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float32) per array of ``arrays``.  Arrays are taken smallest first; one that
+    does not fit its share of what is left of DUMP_BUDGET is written as a fixed sample of its flattened elements -- one
+    element per stride, at an offset drawn from a seeded generator -- so that two runs of the same workload write the
+    same positions and two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left, todo = DUMP_BUDGET, sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        a = t.detach().float()
+        cap = max(1, left // (len(todo) - i) // 4)
+        if a.numel() > cap:
+            n = a.numel()
+            stride = -(-n // cap)
+            idx = torch.arange(0, n, stride)
+            off = torch.randint(0, stride, idx.shape, generator=torch.Generator().manual_seed(1234))
+            a = a.reshape(-1)[(idx + off).clamp_(max=n - 1).to(a.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def training_outputs(model, arena, optim, loss):
+    """What a caller of the training step holds after it: the loss, the model's parameters and Adam's first moment of
+    each.  Parameters are taken in ``model.named_parameters()`` order, each in its own shape, flattened and concatenated:
+    the arena's grouping, alignment gaps and zero padding do not show, so two builds that lay the arena out differently
+    still dump the same vector for the same weights."""
+    named = list(model.named_parameters())
+    return {"loss": loss,
+            "params": torch.cat([p.detach().reshape(-1) for _, p in named]),
+            "adam_exp_avg": torch.cat([arena._slice(optim.exp_avg, p).reshape(-1) for _, p in named])}
+
+
+def m4c_decode_bench(args, device, world, rank, dist, B, seed, dump_dir=None):
     """SECONDARY diagnostic (not the headline metric): BASELINE configs[3], `configs/mmf_m4c.yaml:92-95` -- samples/s of
     M4C's evaluation path, max_iter = 12 passes of the multimodal transformer per batch (mmf_m4c.py:236-256; the early
     exit is disabled by an unreachable eos index so that every batch costs the same), random weights, synthetic
@@ -473,7 +524,7 @@ def m4c_decode_bench(args, device, world, rank, dist, B, seed):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, _, passes = run()
+        scores, prev, passes = run()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -482,6 +533,8 @@ def m4c_decode_bench(args, device, world, rank, dist, B, seed):
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if dump_dir and rank == 0 and args.steps > 0:
+        dump_outputs(dump_dir, {"scores": scores, "tokens": prev})
     res = None
     if rank == 0:
         res = ({
@@ -505,7 +558,7 @@ def m4c_decode_bench(args, device, world, rank, dist, B, seed):
     return res
 
 
-def decode_bench(args, device, world, rank, dist, B, seed):
+def decode_bench(args, device, world, rank, dist, B, seed, dump_dir=None):
     """SECONDARY diagnostic (not the headline metric): BASELINE configs[4], `configs/vit_mbert_generation.yaml:68-98` --
     the stateful `Decoder` (L=3, d=512, H=8, dff=2048) decoding T=20 tokens per sample over 237 encoder positions with
     batched beam search (openvivqa_amd.beam = beam_search.py's control flow), evaluation mode, random weights, synthetic
@@ -551,7 +604,7 @@ def decode_bench(args, device, world, rank, dist, B, seed):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        tokens, logp = run()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -560,6 +613,8 @@ def decode_bench(args, device, world, rank, dist, B, seed):
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if dump_dir and rank == 0 and args.steps > 0:
+        dump_outputs(dump_dir, {"tokens": tokens, "log_probs": logp})
     res = None
     if rank == 0:
         per_step = dt / args.steps / T
@@ -719,15 +774,14 @@ def main():
         A.manual_seed(b.SEED + rank)
         torch.manual_seed(b.SEED)
         fn = m4c_decode_bench if args.workload == "m4c_decode" else decode_bench
-        res = fn(args, device, world, rank, dist, int(b.BATCH_PER_GPU), int(b.SEED))
+        res = fn(args, device, world, rank, dist, int(b.BATCH_PER_GPU), int(b.SEED), dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(res), flush=True)
         return teardown()
 
-    out, ts, cfg = train_bench(args, args.workload, device, world, rank, dist, dtype)
+    out, ts, cfg = train_bench(args, args.workload, device, world, rank, dist, dtype, dump_dir=args.dump_outputs)
     if rank == 0:
-        b = cfg.BENCH
-        if args.workload == "stack":
+        if args.workload == "stack" and args.full:
             if not args.no_roofline and args.dtype == "bf16":
                 add_rooflines(out, ts, cfg, device)
             if world == 1 and not args.no_secondary and not args.rehearse_comm:
@@ -755,9 +809,10 @@ MODEL_GFLOP_PER_SAMPLE = {
 }
 
 
-def train_bench(args, workload, device, world, rank, dist, dtype, steps=None, warmup=None, repeats=None):
+def train_bench(args, workload, device, world, rank, dist, dtype, steps=None, warmup=None, repeats=None, dump_dir=None):
     """Build the workload (stack = BASELINE's metric; model / cross_modality = whole models through build_model), capture
-    its step, time `steps` steps as the contract says.  Returns (JSON dict on rank 0 else None, TrainStep, config)."""
+    its step, time `steps` steps as the contract says; with ``dump_dir``, write what the last timed step left (loss, fp32
+    parameters, Adam's first moment: ``training_outputs``) there.  Returns (JSON dict on rank 0 else None, TrainStep, config)."""
     import openvivqa_amd as A
     from openvivqa_amd import ops
     from openvivqa_amd.mcan_stack import MCANEncoderStack, synthetic_batch
@@ -896,7 +951,11 @@ def train_bench(args, workload, device, world, rank, dist, dtype, steps=None, wa
     windows = [dt] + [window() for _ in range(max(0, repeats - 1))]
     final_loss = float(loss_buf.item())
     ts.check_device_status()  # (a persistent-kernel hand-off that gave up during the timed steps is an error, not a number)
-    comm_stats = ts.timed_comm_step(*batch) if (dist is not None) else {}
+    if dump_dir and steps > 0:
+        ts.gather_state()  # (sharded optimiser: every chunk's masters and moments to every rank -- a collective)
+        if rank == 0:
+            dump_outputs(dump_dir, training_outputs(model, ts.arena, ts.optim, ts.loss))
+    comm_stats = ts.timed_comm_step(*batch) if (dist is not None and args.full) else {}
     if rank != 0:
         return None, ts, cfg
     import statistics
@@ -997,7 +1056,7 @@ def add_rooflines(out, ts, cfg, device):
 def secondary_lines(args, device, dtype):
     """The other BASELINE configurations on the same clock as the headline: after the headline window,
     in this process, each in try / except -- a failure becomes an "error" string, never a non-zero exit of the headline.
-    Short windows (20 steps / 5 decodes) so that the whole default run stays within a couple of minutes."""
+    Short windows (20 steps / 5 decodes) so that the whole --full run stays within a couple of minutes."""
     import copy
     res = {}
 

@@ -9,8 +9,9 @@ python -m pytest tests/test_train_gpu.py tests/test_kernels_gpu.py -x -q -k "tra
 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-roofline > gpurun_out/bench_plain.json 2> gpurun_out/bench_plain.err
 cat gpurun_out/bench_plain.json
 for ov in 32 0; do
-python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-roofline --rehearse-comm --overlap-mb $ov > gpurun_out/bench_rehearse_$ov.json 2> gpurun_out/bench_rehearse_$ov.err
-cat gpurun_out/bench_rehearse_$ov.json
+RES=${RES:-bench_results}; mkdir -p "$RES"
+python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-roofline --rehearse-comm --overlap-mb $ov --full > "$RES/bench_rehearse_$ov.json" 2> "$RES/bench_rehearse_$ov.err"
+cat "$RES/bench_rehearse_$ov.json"
 done
 cd /tmp && export TMPDIR=/tmp
 for ov in 32 0; do

@@ -15,8 +15,8 @@ tests/test_modules_gpu.py: relative L2 <= 1e-2 and normalised max <= 2e-2; singl
 keep the 1e-2 normalised-max bar.
 Run:  python tests/bf16_noise_floor.py
 """
-import sys, math, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, math, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle as O
 from openvivqa_amd.config import ConfigNode, attention_config
 torch.set_num_threads(8)

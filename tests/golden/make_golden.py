@@ -890,12 +890,26 @@ def g17():
     finish(c)
 
 
+# ---------------------------------------------------------------- G18 reference configs
+def g18():
+    """The MODEL nodes of the five BASELINE configs as the reference's YAML files parse (yaml.safe_load, the loader of
+    configs/utils.py): data only, written as JSON (itself YAML, so ``get_config`` reads the file)."""
+    import yaml
+    out = {}
+    for name in ("mcan", "cross_modality_transformer", "vit_mbert_generation", "mmf_m4c", "saaa"):
+        with open(os.path.join(REF, "configs", name + ".yaml")) as f:
+            out[name] = {"MODEL": yaml.safe_load(f)["MODEL"]}
+    with open(os.path.join(HERE, "G18_reference_configs.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("G18 configs:", sorted(out))
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("cases", nargs="*", help="e.g. g12 (default: all)")
     todo = ap.parse_args().cases
-    table = dict(g1=g1, g2=g2, g3=g3, g4=g4, g5=g5, g6=g6, g7=g7, g8=g8, g8k=g8k, g9=g9, g10=g10, g11=g11, g12=g12, g13=g13, g14=g14, g15=g15, g16=g16, g17=g17)
+    table = dict(g1=g1, g2=g2, g3=g3, g4=g4, g5=g5, g6=g6, g7=g7, g8=g8, g8k=g8k, g9=g9, g10=g10, g11=g11, g12=g12, g13=g13, g14=g14, g15=g15, g16=g16, g17=g17, g18=g18)
     mpath = os.path.join(HERE, "manifest.json")
     if todo and os.path.exists(mpath):
         manifest.update(json.load(open(mpath))["cases"])

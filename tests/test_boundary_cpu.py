@@ -21,7 +21,6 @@ from openvivqa_amd.config import ConfigNode, attention_config, get_config
 from golden_cases import load_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
@@ -66,20 +65,25 @@ def test_config_node_access():
     assert cfg.MODEL.SELF_ENCODER.SELF_ATTENTION.USE_AOA is False
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+def _reference_config(name):
+    """MODEL node of one of the reference's BASELINE configs, exactly as its YAML file parses (G18: the parsed trees,
+    stored as JSON -- itself YAML -- by tests/golden/make_golden.py:g18), read through ``get_config``."""
+    return get_config(os.path.join(GOLDEN, "G18_reference_configs.json"))[name]
+
+
 def test_reference_yamls_load_verbatim():
     """The five BASELINE configs are consumed as they are (yacs replaced by ConfigNode)."""
     with open(os.path.join(GOLDEN, "G10_state_dict_manifest.json")) as f:
         man = json.load(f)
-    mcan = get_config(os.path.join(REF, "configs", "mcan.yaml")).MODEL
+    mcan = _reference_config("mcan").MODEL
     enc = A.build_encoder(mcan.SELF_ENCODER)
     genc = A.build_encoder(mcan.GUIDED_ENCODER)
     assert {k: list(v.shape) for k, v in enc.state_dict().items()} == man["Encoder"]
     assert {k: list(v.shape) for k, v in genc.state_dict().items()} == man["GuidedAttentionEncoder"]
-    cmt = get_config(os.path.join(REF, "configs", "cross_modality_transformer.yaml")).MODEL
+    cmt = _reference_config("cross_modality_transformer").MODEL
     cm = A.build_encoder(cmt.ENCODER)
     assert {k: list(v.shape) for k, v in cm.state_dict().items()} == man["CrossModalityEncoder"]
-    gen = get_config(os.path.join(REF, "configs", "vit_mbert_generation.yaml")).MODEL
+    gen = _reference_config("vit_mbert_generation").MODEL
 
     class Vocab:
         max_answer_length, padding_idx = 20, 0
@@ -88,10 +92,10 @@ def test_reference_yamls_load_verbatim():
             return 100
     dec = A.build_decoder(gen.DECODER, Vocab())
     assert dec.fc.weight.shape == (100, 512) and len(dec.layers) == gen.DECODER.LAYERS
-    for name in ("mmf_m4c.yaml", "saaa.yaml"):
-        assert "MODEL" in get_config(os.path.join(REF, "configs", name))
+    for name in ("mmf_m4c", "saaa"):
+        assert "MODEL" in _reference_config(name)
     # the whole MCAN model resolves through build_model from the unmodified YAML (only DEVICE is overridden)
-    mcan_model_cfg = get_config(os.path.join(REF, "configs", "mcan.yaml")).MODEL
+    mcan_model_cfg = _reference_config("mcan").MODEL
     mcan_model_cfg["DEVICE"] = "cpu"
 
     class ClsVocab:

@@ -663,7 +663,7 @@ def test_bench_launcher_two_ranks_on_this_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, OVQA_REHEARSE_BACKEND="gloo", OVQA_NO_BUILD="1", PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--repeats", "1", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True,
+                        "--repeats", "1", "--no-cpu-baseline", "--no-roofline", "--full"], env=env, capture_output=True, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
