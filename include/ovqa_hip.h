@@ -291,7 +291,9 @@ int ovqa_grouped_partial_reduce(const ovqa_reduce_problem* problems, int32_t n_p
  *   att_drop (may be NULL / p == 0): dropout on the attention PROBABILITIES, p~ = p * keep/(1-p) with the
  *   element index ((b*H+h)*nq+i)*nk+j -- what transformers' BertSelfAttention does inside M4C's multimodal
  *   transformer (models/mmf_m4c.py:349-351); `att` then holds p~.  The reference's own attention modules have
- *   none (attentions.py:56-57).  Runs on the VALU kernels (the MFMA kernels cover p == 0).
+ *   none (attentions.py:56-57).  bf16 runs on the MFMA kernels within their shapes (d in {64, 96, 128},
+ *   n_k <= 192, <= 256 for d = 64; forward and the two-kernel backward), with the same keep decisions as
+ *   the VALU kernels; fp32, and d_att / d_lse in the backward, run on the VALU kernels.
  * ------------------------------------------------------------------------- */
 int ovqa_attention_fwd(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk,
                        const void* v, int64_t ldv, const float* mask,

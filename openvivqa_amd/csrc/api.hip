@@ -553,6 +553,8 @@ int ovqa_attention_bwd(int dtype, const void* d_o, int64_t lddo, const void* q, 
   if (B == 0 || nq == 0) return OVQA_OK;
   OVQA_REQUIRE(d_o && q && k && v && o && dq && dk_ && dv_, OVQA_ERR_BAD_ARG, "attention_bwd: null pointer");
   OVQA_REQUIRE(B * H <= 0x7fffffff, OVQA_ERR_UNSUPPORTED, "attention_bwd: B*H too large");
+  OVQA_REQUIRE(B * H * nq * nk < (1ll << 32) || !att_drop || att_drop->p <= 0.f, OVQA_ERR_UNSUPPORTED,
+               "attention_bwd: dropout on more than 2^32 probabilities");
   ovqa::AttnBwdArgs a{d_o, q, k, v, o, d_att, lddo, ldq, ldk, ldv, ldo, lse, mask, msb, msh, msq, dq, dk_, dv_,
                       lddq, lddk, lddv, delta, (int)B, (int)H, (int)nq, (int)nk, (int)dk, (int)dv, scale,
                       make_drop_args(att_drop), d_lse};

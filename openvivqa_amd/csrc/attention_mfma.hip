@@ -141,14 +141,34 @@ __device__ __forceinline__ bf16 packed_lo(float v) {
   return __builtin_bit_cast(bf16, (unsigned short)(__float_as_uint(v) >> 16));
 }
 
+// Dropout multipliers (keep / (1 - p) or 0) of the 4 consecutive flat elements idx .. idx+3: the run of keys a lane owns in
+// one group of a 32x32 accumulator tile (acc_row(4*g4 + e) = key0 + e).  Same decisions as drop_keep(): element 2m / 2m+1
+// takes the low / high 16 bits of the hash of pair m.  Two hashes when idx is even; an odd idx (odd n_k, odd row) straddles
+// three pairs.
+__device__ __forceinline__ void drop_mul4(const DropState& s, uint32_t idx, float (&m)[4]) {
+  const uint32_t pr = idx >> 1;
+  const uint32_t h0 = drop_pair_hash(s, pr), h1 = drop_pair_hash(s, pr + 1);
+  uint32_t f[4];
+  if ((idx & 1u) == 0) {
+    f[0] = h0 & 0xFFFFu; f[1] = h0 >> 16; f[2] = h1 & 0xFFFFu; f[3] = h1 >> 16;
+  } else {
+    const uint32_t h2 = drop_pair_hash(s, pr + 2);
+    f[0] = h0 >> 16; f[1] = h1 & 0xFFFFu; f[2] = h1 >> 16; f[3] = h2 & 0xFFFFu;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; e++) m[e] = f[e] >= s.thresh ? s.inv_keep : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // grid.x = ceil(B*H / G), grid.y = ceil(nq / (32*W)) ; W = query tiles per problem in this workgroup
 // ROWMASK: the mask is one fp32 row per (b,h) (key padding; staged in LDS, -inf beyond n_k) -- the common case,
-// compiled without the per-element bound checks / global mask reads; WANT_ATT: also write the probabilities.
+// compiled without the per-element bound checks / global mask reads; WANT_ATT: also write the probabilities; DROP: dropout
+// on the probabilities (a.drop.p > 0, element index ((b*H+h)*nq+q)*nk+key as in attention_simple.hip): mx, sum and lse
+// are those of the undropped P, the packed P.V / o_lo operand is p * keep/(1-p), so o + o_lo = P~ V and att = P~.
 // One wave: 32 queries (q0 .. q0+31 of problem (b, h), staged at rows qrow0.. of the Q image) against all keys of the
 // problem's K / V images; writes o, lse (and the probabilities).  Shared by the plain forward kernel and by the fused
 // projection + attention kernel.
-template <int NKT, bool ROWMASK, bool WANT_ATT, int D>
+template <int NKT, bool ROWMASK, bool WANT_ATT, int D, bool DROP = false>
 __device__ __forceinline__ void attn_fwd_core(const ovqa::AttnArgs& a, int b, int h, int q0, int qrow0, const char* Qs,
                                               const char* Ks, const char* Vs, const float* mlds, int lane) {
   constexpr int KS = Img<D>::KS, DT = Img<D>::DT;
@@ -202,16 +222,35 @@ __device__ __forceinline__ void attn_fwd_core(const ovqa::AttnArgs& a, int b, in
     }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   float sum = 0.f;
+  if constexpr (DROP) {
+    const DropState ds = drop_init(a.drop);
+    const uint32_t rbase = (uint32_t)((((int64_t)b * a.H + h) * nq + q) * nk);
 #pragma unroll
-  for (int t = 0; t < NKT; t++)
+    for (int t = 0; t < NKT; t++)
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const float p = exp2_fast((st[t][r] - mx) * LOG2E);
-      sum += p;
-      // from here on the register holds p as TWO bf16: its bf16 value (low half: the operand of P.V) and the bf16 of
-      // what that rounding dropped (high half: the operand of the o_lo pass) -- 16 bits of p in the same register
-      st[t][r] = pack_hi_lo(p);
-    }
+      for (int g4 = 0; g4 < 4; g4++) {
+        const int key0 = t * 32 + 8 * g4 + 4 * (lane >> 5);
+        float dm[4] = {0.f, 0.f, 0.f, 0.f};
+        if (qok && key0 < nk) drop_mul4(ds, rbase + (uint32_t)key0, dm);  // keys >= nk (p == 0) hash nothing
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const float p = exp2_fast((st[t][4 * g4 + e] - mx) * LOG2E);
+          sum += p;
+          st[t][4 * g4 + e] = pack_hi_lo(p * dm[e]);
+        }
+      }
+  } else {
+#pragma unroll
+    for (int t = 0; t < NKT; t++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const float p = exp2_fast((st[t][r] - mx) * LOG2E);
+        sum += p;
+        // from here on the register holds p as TWO bf16: its bf16 value (low half: the operand of P.V) and the bf16 of
+        // what that rounding dropped (high half: the operand of the o_lo pass) -- 16 bits of p in the same register
+        st[t][r] = pack_hi_lo(p);
+      }
+  }
   sum += __shfl_xor(sum, 32, 64);
   const float inv = 1.f / sum;
   if (qok && a.lse && lane < 32) a.lse[((int64_t)b * a.H + h) * nq + q] = mx + __logf(sum);
@@ -284,7 +323,7 @@ __device__ __forceinline__ void attn_fwd_core(const ovqa::AttnArgs& a, int b, in
   }
 }
 
-template <int NKT, bool ROWMASK, bool WANT_ATT, int D = 64>
+template <int NKT, bool ROWMASK, bool WANT_ATT, int D = 64, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(ovqa::AttnArgs a, int W, int G) {
   constexpr int PITCH = Img<D>::PITCH;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -322,7 +361,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(ovqa::AttnArgs a, in
   const char* Ks = Qs + q_rows * PITCH;
   const char* Vs = Ks + NKT * 32 * PITCH;
   const float* mlds = reinterpret_cast<const float*>(Vs + NKT * 32 * PITCH);
-  attn_fwd_core<NKT, ROWMASK, WANT_ATT, D>(a, b, h, q0, tq * 32, Qs, Ks, Vs, mlds, lane);
+  attn_fwd_core<NKT, ROWMASK, WANT_ATT, D, DROP>(a, b, h, q0, tq * 32, Qs, Ks, Vs, mlds, lane);
 }
 
 // ------------------------------------------------------------------------- fused Q/K/V projection + attention
@@ -640,7 +679,9 @@ __global__ __launch_bounds__(512 * NH) void attn_q_fwd_mfma_kernel(QAttnArgs g) 
 // Kernel A: one wave = 32 queries (columns).  delta_q = dO_q . O_q ;  for every key tile:
 //   S^T = K Q^T, dP^T = V dO^T, P^T = exp(S^T*scale + mask - lse_q), dS^T = P^T (dP^T - delta_q),
 //   dQ^T += K^T dS^T   (K^T through transposing reads, dS^T straight from the accumulator registers).
-template <bool ROWMASK, int D = 64>
+// DROP (dropout on the probabilities, a.drop.p > 0): dS^T = P^T (dP^T * keep/(1-p) - delta_q), the keep decisions those
+// of the forward (element ((b*H+h)*nq+q)*nk+key); delta = dO . (o + o_lo) is already rowsum(P~ * dP).
+template <bool ROWMASK, int D = 64, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs a, int W, int G, int nkt) {
   constexpr int PITCH = Img<D>::PITCH, KS = Img<D>::KS, DT = Img<D>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -709,6 +750,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
   const float lse = a.lse[((int64_t)b * a.H + h) * nq + qc];
   if (qok && lane < 32) a.delta[((int64_t)b * a.H + h) * nq + q] = delta;
   const float* mrow = a.mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh + (int64_t)qc * a.msq : nullptr;
+  DropState dst{};
+  uint32_t rbase = 0;
+  if constexpr (DROP) {
+    dst = drop_init(a.drop);
+    rbase = (uint32_t)((((int64_t)b * a.H + h) * nq + qc) * nk);
+  }
 
   bf16x8 qf[KS], gf[KS];
 #pragma unroll
@@ -732,17 +779,38 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
       dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(Vs, t * 32, ks, lane), gf[ks], dp, 0, 0, 0);
     }
     float ds[16];
+    if constexpr (DROP) {
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const int key = t * 32 + acc_row(r, lane);
-      float p;
-      if (row_mask) {
-        p = exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);  // -inf beyond nk -> 0
-      } else {
-        p = 0.f;
-        if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
+      for (int g4 = 0; g4 < 4; g4++) {
+        const int key0 = t * 32 + 8 * g4 + 4 * (lane >> 5);
+        float dm[4] = {0.f, 0.f, 0.f, 0.f};
+        if (qok && key0 < nk) drop_mul4(dst, rbase + (uint32_t)key0, dm);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const int r = 4 * g4 + e, key = key0 + e;
+          float p;
+          if (row_mask) {
+            p = exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);
+          } else {
+            p = 0.f;
+            if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
+          }
+          ds[r] = p * (dp[r] * dm[e] - delta);
+        }
       }
-      ds[r] = p * (dp[r] - delta);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int key = t * 32 + acc_row(r, lane);
+        float p;
+        if (row_mask) {
+          p = exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);  // -inf beyond nk -> 0
+        } else {
+          p = 0.f;
+          if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
+        }
+        ds[r] = p * (dp[r] - delta);
+      }
     }
 #pragma unroll
     for (int s = 0; s < 2; s++) {
@@ -771,7 +839,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
 // Kernel B: one wave = 32 keys (columns).  For every query tile (rows):
 //   S = Q K^T, dP = dO V^T, P = exp(S*scale + mask - lse_row), dS = P (dP - delta_row),
 //   dV^T += dO^T P ,  dK^T += Q^T dS    (dO^T / Q^T through transposing reads).
-template <bool ROWMASK, int D = 64>
+// DROP: dV^T += dO^T P~ and dS = P (dP * keep/(1-p) - delta_row), P~ = P * keep/(1-p).  A lane walks a key COLUMN, so
+// its 4 consecutive accumulator rows are 4 queries n_k elements apart: the index is built per element from
+// (b, h, query, key) and each element hashes its own pair.
+template <bool ROWMASK, int D = 64, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArgs a, int W, int G, int nqt) {
   constexpr int PITCH = Img<D>::PITCH, KS = Img<D>::KS, DT = Img<D>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -819,6 +890,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArg
   const float* mcol = a.mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh + (kok ? key : 0) : nullptr;
   constexpr bool row_mask = ROWMASK;  // key-padding mask: one value per key column, i.e. per lane
   const float mconst = (row_mask && mcol) ? mcol[0] : 0.f;
+  DropState dst{};
+  uint32_t pbase = 0;  // ((b*H+h)*nq) * nk + key: element (qi, key) is pbase + qi * nk
+  if constexpr (DROP) {
+    dst = drop_init(a.drop);
+    pbase = (uint32_t)(((int64_t)b * a.H + h) * nq * nk + key);
+  }
 
   bf16x8 kf[KS], vf[KS];
 #pragma unroll
@@ -850,8 +927,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArg
         const float mv = row_mask ? mconst : (mcol ? mcol[(int64_t)qi * a.msq] : 0.f);
         pv = exp2_fast((s_[r] * a.scale + mv - ls[qi]) * LOG2E);
       }
-      p[r] = pv;
-      ds[r] = pv * (dp[r] - ls[q_rows + qi]);
+      if constexpr (DROP) {
+        const float m = (qi < nq && kok && drop_keep(dst, pbase + (uint32_t)qi * (uint32_t)nk)) ? dst.inv_keep : 0.f;
+        p[r] = pv * m;
+        ds[r] = pv * (dp[r] * m - ls[q_rows + qi]);
+      } else {
+        p[r] = pv;
+        ds[r] = pv * (dp[r] - ls[q_rows + qi]);
+      }
     }
 #pragma unroll
     for (int s = 0; s < 2; s++) {
@@ -1987,26 +2070,31 @@ inline int fit_tiles(int n, size_t fixed_bytes, size_t bytes_per_tile) {
   return W;
 }
 
-template <int NKT, bool ROWMASK, bool WANT_ATT, int D>
+template <int NKT, bool ROWMASK, bool WANT_ATT, int D, bool DROP>
 int launch_fwd_t(const ovqa::AttnArgs& a, hipStream_t st) {
   constexpr int PITCH = Img<D>::PITCH;
   const int W = fit_tiles(a.nq, (size_t)2 * NKT * 32 * PITCH + NKT * 32 * 4, (size_t)32 * PITCH);
   const size_t prob = (size_t)(32 * W + 2 * NKT * 32) * PITCH + NKT * 32 * 4;
   const int G = pack_factor(W, prob);
   const size_t lds = (size_t)G * prob;
-  int rc = ensure_lds(attn_fwd_mfma_kernel<NKT, ROWMASK, WANT_ATT, D>, lds, "attention_fwd(mfma)");
+  int rc = ensure_lds(attn_fwd_mfma_kernel<NKT, ROWMASK, WANT_ATT, D, DROP>, lds, "attention_fwd(mfma)");
   if (rc != OVQA_OK) return rc;
   const int64_t nprob = (int64_t)a.B * a.H;
   dim3 grid((unsigned)((nprob + G - 1) / G), (unsigned)((a.nq + 32 * W - 1) / (32 * W)));
-  OVQA_LAUNCH_TIMED((attn_fwd_mfma_kernel<NKT, ROWMASK, WANT_ATT, D>), grid, dim3(256), lds, st, a, W, G);
+  OVQA_LAUNCH_TIMED((attn_fwd_mfma_kernel<NKT, ROWMASK, WANT_ATT, D, DROP>), grid, dim3(256), lds, st, a, W, G);
   return ovqa_check_launch("attention_fwd(mfma)");
+}
+
+template <int NKT, int D, bool DROP>
+int launch_fwd_m(const ovqa::AttnArgs& a, hipStream_t st) {
+  const bool rowmask = a.msq == 0, att = a.att != nullptr;
+  if (rowmask) return att ? launch_fwd_t<NKT, true, true, D, DROP>(a, st) : launch_fwd_t<NKT, true, false, D, DROP>(a, st);
+  return att ? launch_fwd_t<NKT, false, true, D, DROP>(a, st) : launch_fwd_t<NKT, false, false, D, DROP>(a, st);
 }
 
 template <int NKT, int D>
 int launch_fwd(const ovqa::AttnArgs& a, hipStream_t st) {
-  const bool rowmask = a.msq == 0, att = a.att != nullptr;
-  if (rowmask) return att ? launch_fwd_t<NKT, true, true, D>(a, st) : launch_fwd_t<NKT, true, false, D>(a, st);
-  return att ? launch_fwd_t<NKT, false, true, D>(a, st) : launch_fwd_t<NKT, false, false, D>(a, st);
+  return a.drop.p > 0.f ? launch_fwd_m<NKT, D, true>(a, st) : launch_fwd_m<NKT, D, false>(a, st);
 }
 
 template <int D>
@@ -2020,9 +2108,9 @@ int launch_fwd_d(const ovqa::AttnArgs& a, hipStream_t st) {
   return OVQA_ERR_UNSUPPORTED;
 }
 
-// two-kernel backward (dQ, then dK/dV) for any supported head size
-template <int D>
-int launch_bwd_two(const ovqa::AttnBwdArgs& a, hipStream_t st) {
+// two-kernel backward (dQ, then dK/dV) for any supported head size; the only form with dropout on the probabilities
+template <int D, bool DROP>
+int launch_bwd_two_t(const ovqa::AttnBwdArgs& a, hipStream_t st) {
   constexpr int PITCH = Img<D>::PITCH;
   const int64_t nprob = (int64_t)a.B * a.H;
   const bool rowmask = a.msq == 0;
@@ -2032,12 +2120,12 @@ int launch_bwd_two(const ovqa::AttnBwdArgs& a, hipStream_t st) {
     const size_t prob = (size_t)(2 * 32 * W + 2 * nkt * 32) * PITCH + nkt * 32 * 4;
     const int G = pack_factor(W, prob);
     const size_t lds = (size_t)G * prob;
-    int rc = rowmask ? ensure_lds(attn_bwd_dq_mfma_kernel<true, D>, lds, "attention_bwd(mfma,dq)")
-                     : ensure_lds(attn_bwd_dq_mfma_kernel<false, D>, lds, "attention_bwd(mfma,dq)");
+    int rc = rowmask ? ensure_lds(attn_bwd_dq_mfma_kernel<true, D, DROP>, lds, "attention_bwd(mfma,dq)")
+                     : ensure_lds(attn_bwd_dq_mfma_kernel<false, D, DROP>, lds, "attention_bwd(mfma,dq)");
     if (rc != OVQA_OK) return rc;
     dim3 grid((unsigned)((nprob + G - 1) / G), (unsigned)((a.nq + 32 * W - 1) / (32 * W)));
-    if (rowmask) OVQA_LAUNCH_TIMED((attn_bwd_dq_mfma_kernel<true, D>), grid, dim3(256), lds, st, a, W, G, nkt);
-    else OVQA_LAUNCH_TIMED((attn_bwd_dq_mfma_kernel<false, D>), grid, dim3(256), lds, st, a, W, G, nkt);
+    if (rowmask) OVQA_LAUNCH_TIMED((attn_bwd_dq_mfma_kernel<true, D, DROP>), grid, dim3(256), lds, st, a, W, G, nkt);
+    else OVQA_LAUNCH_TIMED((attn_bwd_dq_mfma_kernel<false, D, DROP>), grid, dim3(256), lds, st, a, W, G, nkt);
     rc = ovqa_check_launch("attention_bwd(mfma,dq)");
     if (rc != OVQA_OK) return rc;
   }
@@ -2047,14 +2135,19 @@ int launch_bwd_two(const ovqa::AttnBwdArgs& a, hipStream_t st) {
     const size_t prob = (size_t)(2 * nqt * 32 + 2 * 32 * W) * PITCH + 2 * nqt * 32 * 4;
     const int G = pack_factor(W, prob);
     const size_t lds = (size_t)G * prob;
-    int rc = rowmask ? ensure_lds(attn_bwd_dkv_mfma_kernel<true, D>, lds, "attention_bwd(mfma,dkv)")
-                     : ensure_lds(attn_bwd_dkv_mfma_kernel<false, D>, lds, "attention_bwd(mfma,dkv)");
+    int rc = rowmask ? ensure_lds(attn_bwd_dkv_mfma_kernel<true, D, DROP>, lds, "attention_bwd(mfma,dkv)")
+                     : ensure_lds(attn_bwd_dkv_mfma_kernel<false, D, DROP>, lds, "attention_bwd(mfma,dkv)");
     if (rc != OVQA_OK) return rc;
     dim3 grid((unsigned)((nprob + G - 1) / G), (unsigned)((a.nk + 32 * W - 1) / (32 * W)));
-    if (rowmask) OVQA_LAUNCH_TIMED((attn_bwd_dkv_mfma_kernel<true, D>), grid, dim3(256), lds, st, a, W, G, nqt);
-    else OVQA_LAUNCH_TIMED((attn_bwd_dkv_mfma_kernel<false, D>), grid, dim3(256), lds, st, a, W, G, nqt);
+    if (rowmask) OVQA_LAUNCH_TIMED((attn_bwd_dkv_mfma_kernel<true, D, DROP>), grid, dim3(256), lds, st, a, W, G, nqt);
+    else OVQA_LAUNCH_TIMED((attn_bwd_dkv_mfma_kernel<false, D, DROP>), grid, dim3(256), lds, st, a, W, G, nqt);
     return ovqa_check_launch("attention_bwd(mfma,dkv)");
   }
+}
+
+template <int D>
+int launch_bwd_two(const ovqa::AttnBwdArgs& a, hipStream_t st) {
+  return a.drop.p > 0.f ? launch_bwd_two_t<D, true>(a, st) : launch_bwd_two_t<D, false>(a, st);
 }
 
 // (The role-split backward fills its Q / dO / K / V images by direct-to-LDS loads where the mask is a key row; through
@@ -2063,6 +2156,7 @@ int launch_bwd_two(const ovqa::AttnBwdArgs& a, hipStream_t st) {
 int launch_bwd(const ovqa::AttnBwdArgs& a, hipStream_t st) {
   if (a.dk == 96) return launch_bwd_two<96>(a, st);
   if (a.dk == 128) return launch_bwd_two<128>(a, st);
+  if (a.drop.p > 0.f) return launch_bwd_two<64>(a, st);  // the role-split / merged forms have no dropout
   const int64_t nprob = (int64_t)a.B * a.H;
   const bool rowmask = a.msq == 0;
   if (a.nk > 32 && a.nk <= 128 && a.nq <= 128) {  // one launch, role-split waves
@@ -2124,10 +2218,11 @@ namespace ovqa {
 bool mfma_attention_bwd_supported(const AttnBwdArgs& a) {
   auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
-  // gradients of the returned attention weights / log-sum-exp and dropout on the probabilities: VALU kernels
+  // gradients of the returned attention weights / log-sum-exp: VALU kernels (dropout on the probabilities: the
+  // two-kernel form, launch_bwd_two)
   const bool d_ok = a.dk == a.dv && (a.dk == 64 || a.dk == 96 || a.dk == 128);
   const int n_max = a.dk == 64 ? 256 : 192;  // what stays LDS-resident next to two 32-row tiles of the other side
-  return a.d_att == nullptr && a.d_lse == nullptr && a.drop.p <= 0.f && d_ok && a.nk >= 1 &&
+  return a.d_att == nullptr && a.d_lse == nullptr && d_ok && a.nk >= 1 &&
          a.nk <= n_max && a.nq >= 1 && a.nq <= n_max &&
          a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.lddo % 8 == 0 && a.ldo % 4 == 0 && a.lddq % 4 == 0 &&
          a.lddk % 4 == 0 && a.lddv % 4 == 0 && al(a.q) && al(a.k) && al(a.v) && al(a.d_o) && al8(a.o) && al8(a.dq) &&
@@ -2139,7 +2234,7 @@ int mfma_attention_bwd(const AttnBwdArgs& a, hipStream_t st) { return launch_bwd
 bool mfma_attention_supported(const AttnArgs& a) {
   auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   const bool d_ok = a.dk == a.dv && (a.dk == 64 || a.dk == 96 || a.dk == 128);
-  return a.drop.p <= 0.f && d_ok && a.nk >= 1 && a.nk <= (a.dk == 64 ? 256 : 192) && a.nq >= 1 && a.ldq % 8 == 0 &&
+  return d_ok && a.nk >= 1 && a.nk <= (a.dk == 64 ? 256 : 192) && a.nq >= 1 && a.ldq % 8 == 0 &&
          a.ldk % 8 == 0 &&
          a.ldv % 8 == 0 && a.ldo % 4 == 0 && al(a.q) && al(a.k) && al(a.v) && (((uintptr_t)a.o & 7) == 0);
 }

@@ -49,7 +49,7 @@ def wgrad_queue():
     return _wgrad_queue
 
 
-def _wgrad(arena, dy, x, w_params, b_params):
+def _wgrad(arena, dy, x, w_params, b_params, defer_ok=True):
     """dW/db of a (possibly packed) linear into the arena's grad buffer.
 
     bf16: weight AND bias gradient are queued and computed at the END of the backward pass by one
@@ -61,7 +61,7 @@ def _wgrad(arena, dy, x, w_params, b_params):
     gb, acc_b = arena.grad_views(b_params) if b_params else (None, False)
     if wgrad_observer is not None:
         wgrad_observer(gw)
-    defer = (dy.dtype == torch.bfloat16 and dy.is_cuda and dy.shape[-1] % 8 == 0 and x.shape[-1] % 8 == 0
+    defer = (defer_ok and dy.dtype == torch.bfloat16 and dy.is_cuda and dy.shape[-1] % 8 == 0 and x.shape[-1] % 8 == 0
              and os.environ.get("OVQA_DEFER_WGRAD", "1") != "0")
     if not defer:
         ops.linear_bwd_weight(dy, x, gw, gb, accumulate=acc_w, accumulate_db=acc_b)
@@ -593,7 +593,7 @@ class _Linear(Function):
         arena, lin = st["arena"], st["lin"]
         (x,) = ctx.saved_tensors
         dy = _pad_cols(_c(dy), arena.foot[id(lin.weight)][0])
-        _wgrad(arena, dy, x, [lin.weight], [lin.bias] if lin.bias is not None else [])
+        _wgrad(arena, dy, x, [lin.weight], [lin.bias] if lin.bias is not None else [], defer_ok=not st["eager_wgrad"])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _dx(arena, dy, [lin.weight])
@@ -644,10 +644,13 @@ def linear_gelu_dropout(x, lin, arena, drop):
     return y if y.shape[-1] == lin.weight.shape[0] else y[..., :lin.weight.shape[0]].contiguous()
 
 
-def linear(x, lin, arena):
-    """y = lin(x) through the HIP GEMM (x is cast to the arena's compute dtype by the caller)."""
+def linear(x, lin, arena, eager_wgrad=False):
+    """y = lin(x) through the HIP GEMM (x is cast to the arena's compute dtype by the caller).  ``eager_wgrad``: the weight
+    gradient is stored when this product's backward runs instead of by the grouped launch at the end of the pass -- for a
+    weight that ALSO receives an autograd gradient in the same pass (M4C's answer table, classifier.weight): the product
+    runs first in the backward pass, so it overwrites the slot and autograd's later accumulation adds to it."""
     params = [lin.weight] + ([lin.bias] if lin.bias is not None else [])
-    st = dict(arena=arena, lin=lin, params=params)
+    st = dict(arena=arena, lin=lin, params=params, eager_wgrad=eager_wgrad)
     if torch.is_grad_enabled():
         return _Linear.apply(x, st, *params)
     w, bias = _lin_operands(arena, lin)
@@ -1014,6 +1017,28 @@ class _ClassifyLogSoftmax(Function):
         _wgrad(arena, dy, x, [lin.weight], [lin.bias] if lin.bias is not None else [])
         dx = _dx(arena, dy, [lin.weight]) if ctx.needs_input_grad[0] else None
         return dx, None, *([None] * len(st["params"]))
+
+
+class _LogSoftmax(Function):
+    @staticmethod
+    def forward(ctx, x):
+        logp = ops.log_softmax_fwd(x)
+        ctx.save_for_backward(logp)
+        return logp
+
+    @staticmethod
+    def backward(ctx, g):
+        (logp,) = ctx.saved_tensors
+        return ops.log_softmax_bwd(_c(g.float()), logp, logp.shape[1], torch.float32)
+
+
+def log_softmax(x):
+    """log_softmax over the last dimension of fp32 rows x [..., n] (HIP kernels both ways) -> fp32 [..., n]."""
+    lead = x.shape[:-1]
+    x2 = _c(x.float()).reshape(-1, x.shape[-1])
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _LogSoftmax.apply(x2).view(*lead, -1)
+    return ops.log_softmax_fwd(x2).view(*lead, -1)
 
 
 def classify_log_softmax(x, lin, arena):

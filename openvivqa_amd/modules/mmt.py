@@ -8,8 +8,8 @@ fused blocks of the hot path -- MHA block (QKV GEMM, attention with an additive 
 GEMM + dropout + residual, LayerNorm eps 1e-12) and FFN block (GEMM+GELU, GEMM + dropout + residual, LayerNorm).
 Heads of 96 features (768/8) run on the MFMA attention kernels (256-byte LDS image rows; two-kernel backward).
 
-Dropout on the attention PROBABILITIES (attention_probs_dropout_prob, training only) runs inside the VALU attention
-kernels (ovqa_attention_fwd/bwd ``att_drop``); evaluation / decoding (BASELINE config 4) has none.
+Dropout on the attention PROBABILITIES (attention_probs_dropout_prob, training only) runs inside the MFMA attention
+kernels (ovqa_attention_fwd/bwd ``att_drop``; the two-kernel backward); evaluation / decoding (BASELINE config 4) has none.
 
 ``PrevPredEmbeddings`` / ``MMT``: mmf_m4c.py:399-459 / 282-364.
 """
@@ -94,7 +94,7 @@ class BertLayer(nn.Module):
                           a.self.value.weight, a.self.value.bias, a.output.dense.weight, a.output.dense.bias,
                           ln1.weight, ln1.bias],
                   drop=rt.dropout_spec(a.output.dropout.p, self._sites[0], self.training, x.device),
-                  # dropout on the attention probabilities (HF BertSelfAttention): training only, VALU attention kernels
+                  # dropout on the attention probabilities (HF BertSelfAttention): training only, inside the attention kernels
                   att_drop=rt.dropout_spec(a.self.dropout.p, self._sites[2], self.training, x.device))
         x = Fn.mha_block(x, x, x, mask, st)
         ffn = SimpleNamespace(fc1=self.intermediate.dense, fc2=self.output.dense, layer_norm=self.output.LayerNorm)

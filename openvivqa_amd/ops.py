@@ -657,7 +657,8 @@ def _lo_buffer(lo_out, like):
 
 def attention_fwd(q, k, v, mask, H, scale=None, need_att=False, save_lse=True, att_drop=None, lo_out=None):
     """q [B,nq,H*dk], k [B,nk,H*dk], v [B,nk,H*dv] (row-strided views allowed) -> o [B,nq,H*dv], lse, att.
-    ``att_drop`` (DropSpec): dropout on the attention probabilities (BERT-style; VALU kernels)."""
+    ``att_drop`` (DropSpec): dropout on the attention probabilities (BERT-style; bf16 on the MFMA kernels within their
+    shapes, the same keep decisions as the VALU kernels)."""
     _dev(q)
     lib = _lib.load()
     B, nq = q.shape[0], q.shape[1]
