@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define OVQA_ABI_VERSION 10
+#define OVQA_ABI_VERSION 11
 
 typedef enum {
   OVQA_OK = 0,
@@ -65,6 +65,15 @@ const char* ovqa_last_error(void);
  * single form).  With OVQA_REQUIRE_MFMA=1 in the environment a bf16 call that would fall back returns
  * OVQA_ERR_UNSUPPORTED instead, so a test can assert which kernel it validated. */
 const char* ovqa_last_dispatch(void);
+/* Launch log (diagnostic, ABI 11): which kernel INSTANTIATION each launch on this thread ran, so a test can assert the
+ * route a shape takes.  ovqa_launch_log_clear() empties this thread's log; ovqa_launch_log(i) = the i-th launch since then
+ * as "<kernel expression at the launch site> @ <__PRETTY_FUNCTION__ of the launching function>" -- the second part's
+ * [NAME = value, ...] bindings give the template arguments the first leaves symbolic -- or NULL past the end.  The
+ * returned text is valid until the next ovqa_launch_log call on the thread.  The first 256 launches are kept.  Every
+ * launch of the MFMA GEMM and attention kernels is logged (timed or not); recording is a host-side pointer store (no
+ * device work, no synchronisation, safe under stream capture). */
+void ovqa_launch_log_clear(void);
+const char* ovqa_launch_log(int i);
 /* Launch timing (diagnostic, used by bench.py's roofline figure).  Between ovqa_launch_timing_begin(max) and
  * ovqa_launch_timing_end(), every launch of the bf16 GEMM kernels behind ovqa_linear_fwd / ovqa_linear_fwd_res32 /
  * ovqa_linear_bwd_data / ovqa_linear_bwd_data_wt and (ABI 6) of the MFMA attention kernels behind ovqa_attention_fwd / _bwd /

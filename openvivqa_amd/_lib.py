@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libovqa_hip.so")
 
 OVQA_F32, OVQA_BF16 = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL = 0, 1, 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_i64, c_int, c_f32, c_vp = C.c_int64, C.c_int, C.c_float, C.c_void_p
 
@@ -80,6 +80,8 @@ SIGNATURES = {
     "ovqa_abi_version": [],
     "ovqa_last_error": [],
     "ovqa_last_dispatch": [],
+    "ovqa_launch_log_clear": [],
+    "ovqa_launch_log": [c_int],
     "ovqa_workspace_bytes": [],
     "ovqa_stream_priority_range": [c_vp, c_vp],
     "ovqa_stream_create": [c_vp, c_int, c_vp, c_int],
@@ -160,7 +162,8 @@ SIGNATURES = {
     "ovqa_lstm_fwd": [c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
     "ovqa_lstm_bwd": [c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
 }
-_RESTYPE = {"ovqa_last_error": C.c_char_p, "ovqa_last_dispatch": C.c_char_p, "ovqa_workspace_bytes": C.c_int64,
+_RESTYPE = {"ovqa_last_error": C.c_char_p, "ovqa_last_dispatch": C.c_char_p, "ovqa_launch_log": C.c_char_p,
+            "ovqa_launch_log_clear": None, "ovqa_workspace_bytes": C.c_int64,
             "ovqa_lstm_saved_bytes": C.c_int64, "ovqa_lstm_scratch_bytes": C.c_int64,
             "ovqa_lstm_persistent_max_batch": C.c_int64}
 
@@ -198,6 +201,61 @@ def last_dispatch() -> str:
     """Kernel family ("mfma" | "simple" | "") the last C-ABI call of this thread ran (ovqa_last_dispatch)."""
     v = load().ovqa_last_dispatch()
     return v.decode() if v else ""
+
+
+def launch_log_clear() -> None:
+    """Empty this thread's launch log (ovqa_launch_log_clear)."""
+    load().ovqa_launch_log_clear()
+
+
+def launch_log() -> list[str]:
+    """Kernel instantiations launched on this thread since launch_log_clear(), in launch order (ovqa_launch_log).
+
+    Each entry is the launch site's kernel expression with the template parameters it leaves symbolic replaced by the
+    bindings of the launching function's __PRETTY_FUNCTION__, whitespace removed, e.g.
+    ``gemm_bf16_glds_kernel<false,false,MEpiBias,2,8,128,128>`` (the ovqa and anonymous namespace
+    qualifiers dropped)."""
+    lib, out, i = load(), [], 0
+    while True:
+        v = lib.ovqa_launch_log(i)
+        if v is None:
+            return out
+        out.append(resolve_launch(v.decode()))
+        i += 1
+
+
+def _split_top(s: str, sep: str = ",") -> list[str]:
+    parts, depth, cur = [], 0, ""
+    for ch in s:
+        if ch in "<([":
+            depth += 1
+        elif ch in ">)]":
+            depth -= 1
+        if ch == sep and depth == 0:
+            parts.append(cur)
+            cur = ""
+        else:
+            cur += ch
+    return parts + [cur]
+
+
+def resolve_launch(entry: str) -> str:
+    """'<kernel expr> @ <pretty function>' -> the kernel expression with the function's template bindings substituted."""
+    import re
+    kernel, _, where = entry.partition(" @ ")
+    kernel = kernel.strip()
+    if kernel.startswith("(") and kernel.endswith(")"):
+        kernel = kernel[1:-1]
+    binds = {}
+    if where.endswith("]") and " [" in where:
+        for b in _split_top(where[where.rindex(" [") + 2:-1]):
+            name, eq, val = b.partition(" = ")
+            if eq:
+                binds[name.strip()] = val.strip()
+    if binds:
+        kernel = re.sub(r"\b[A-Za-z_]\w*\b", lambda m: binds.get(m.group(0), m.group(0)), kernel)
+    kernel = re.sub(r"\s+", "", kernel)
+    return re.sub(r"\(anonymousnamespace\)::|\bovqa::", "", kernel)
 
 
 def check(rc: int, what: str = "") -> None:

@@ -79,6 +79,21 @@ bool ovqa_timer_next(hipEvent_t* start, hipEvent_t* stop) {
   return true;
 }
 
+// launch log: the first kLaunchLogCap launches on this thread since ovqa_launch_log_clear (string literals, never freed)
+static constexpr int kLaunchLogCap = 256;
+static thread_local const char* g_log_kernel[kLaunchLogCap];
+static thread_local const char* g_log_where[kLaunchLogCap];
+static thread_local int g_log_n = 0;
+static thread_local char g_log_line[2048];
+
+void ovqa_launch_note(const char* kernel, const char* where) {
+  if (g_log_n < kLaunchLogCap) {
+    g_log_kernel[g_log_n] = kernel;
+    g_log_where[g_log_n] = where;
+    g_log_n++;
+  }
+}
+
 static inline bool dtype_ok(int d) { return d == OVQA_F32 || d == OVQA_BF16; }
 
 extern "C" {
@@ -86,6 +101,12 @@ extern "C" {
 int ovqa_abi_version(void) { return OVQA_ABI_VERSION; }
 const char* ovqa_last_error(void) { return g_err; }
 const char* ovqa_last_dispatch(void) { return g_dispatch; }
+void ovqa_launch_log_clear(void) { g_log_n = 0; }
+const char* ovqa_launch_log(int i) {
+  if (i < 0 || i >= g_log_n) return nullptr;
+  snprintf(g_log_line, sizeof(g_log_line), "%s @ %s", g_log_kernel[i], g_log_where[i]);
+  return g_log_line;
+}
 
 int ovqa_launch_timing_begin(int max_launches) {
   std::lock_guard<std::mutex> lock(g_timer_mu);

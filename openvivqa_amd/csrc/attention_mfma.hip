@@ -2165,9 +2165,10 @@ int launch_bwd(const ovqa::AttnBwdArgs& a, hipStream_t st) {
     const DoBwdArgs g0{nullptr, 0, nullptr, 0, a, 0};
 #define OVQA_ROLES(NQ, NK, RM)                                                                                        \
   {                                                                                                                   \
-    int rc = ensure_lds(attn_bwd_roles_mfma_kernel<NQ, NK, RM>, lds, "attention_bwd(mfma,roles)");                    \
+    int rc = ensure_lds(attn_bwd_roles_mfma_kernel<NQ, NK, RM, 0, false>, lds, "attention_bwd(mfma,roles)");          \
     if (rc != OVQA_OK) return rc;                                                                                     \
-    OVQA_LAUNCH_TIMED((attn_bwd_roles_mfma_kernel<NQ, NK, RM>), dim3((unsigned)nprob), dim3(512), lds, st, g0, nqt, nkt); \
+    OVQA_LAUNCH_TIMED((attn_bwd_roles_mfma_kernel<NQ, NK, RM, 0, false>), dim3((unsigned)nprob), dim3(512), lds, st, g0,  \
+                      nqt, nkt);                                                                                      \
   }
     if (nqt == 4 && nkt == 4) {  // the 100 x 100 image self-attention: fully unrolled tile loops
       if (rowmask) {

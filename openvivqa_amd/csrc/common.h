@@ -39,8 +39,16 @@ static inline int ovqa_check_launch(const char* what) {
 // take the dispatch packet's own begin / end timestamps -- the kernel's execution time as rocprofv3 --kernel-trace
 // reports it, free of the cost of separate event-record packets around the launch.
 bool ovqa_timer_next(hipEvent_t* start, hipEvent_t* stop);
+// ---- launch log (diagnostic; ovqa_launch_log_clear / ovqa_launch_log) ----------------------------------------------------
+// Host-side only: two string-literal pointers per launch into a small thread-local array -- the kernel expression as written
+// at the launch site (macro parameters such as OVQA_GLDS's tier literals already substituted) and the enclosing function's
+// __PRETTY_FUNCTION__, whose bindings ([PK = ..., Epi = ...]) name the remaining template arguments.  No device work, no
+// synchronisation, safe under stream capture.
+void ovqa_launch_note(const char* kernel, const char* where);
+#define OVQA_NOTE_LAUNCH(kernel) ovqa_launch_note(#kernel, __PRETTY_FUNCTION__)
 #define OVQA_LAUNCH_TIMED(kernel, grid, block, lds, st, ...)                              \
   do {                                                                                    \
+    OVQA_NOTE_LAUNCH(kernel);                                                             \
     hipEvent_t t0_ = nullptr, t1_ = nullptr;                                              \
     if (ovqa_timer_next(&t0_, &t1_))                                                      \
       hipExtLaunchKernelGGL(kernel, grid, block, lds, st, t0_, t1_, 0, __VA_ARGS__);      \

@@ -1241,9 +1241,16 @@ template <typename Epi>
 int launch_batched_nt(const BatchedNT& g, int64_t batch, Epi epi, hipStream_t st, const char* what) {
   const dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)batch);
   const int nk = g.K / 32;
-  if (nk <= 16) hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 1>), grid, dim3(64), 0, st, g, epi);
-  else if (nk <= 32) hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 2>), grid, dim3(128), 0, st, g, epi);
-  else hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 4>), grid, dim3(256), 0, st, g, epi);
+  if (nk <= 16) {
+    OVQA_NOTE_LAUNCH((batched_nt_skinny_kernel<Epi, 1>));
+    hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 1>), grid, dim3(64), 0, st, g, epi);
+  } else if (nk <= 32) {
+    OVQA_NOTE_LAUNCH((batched_nt_skinny_kernel<Epi, 2>));
+    hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 2>), grid, dim3(128), 0, st, g, epi);
+  } else {
+    OVQA_NOTE_LAUNCH((batched_nt_skinny_kernel<Epi, 4>));
+    hipLaunchKernelGGL((batched_nt_skinny_kernel<Epi, 4>), grid, dim3(256), 0, st, g, epi);
+  }
   return ovqa_check_launch(what);
 }
 
@@ -1389,6 +1396,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const ovqa_transpos
 
 int grouped_transpose_bf16(const ovqa_transpose_problem* probs, int n, int max_tiles, hipStream_t st) {
   if (n <= 0 || max_tiles <= 0) return OVQA_OK;
+  OVQA_NOTE_LAUNCH(transpose_bf16_kernel);
   hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)max_tiles, (unsigned)n), dim3(256), 0, st, probs);
   return ovqa_check_launch("grouped_transpose");
 }
@@ -1421,6 +1429,7 @@ int mfma_linear_bwd_weight(const void* dy, int64_t lddy, const void* x, int64_t 
   // the reduction length is passed as "K" of the kernel; K % 8 is not required for k-major operands
   GemmArgs g{(const bf16*)x, ldx, (const bf16*)dy, lddy, (int)K, (int)N, (int)M,
              (int)((K + BT - 1) / BT), (int)((N + BT - 1) / BT)};
+  OVQA_NOTE_LAUNCH(gemm_bf16_wgrad_kernel);
   hipLaunchKernelGGL(gemm_bf16_wgrad_kernel, dim3(g.tiles_r * g.tiles_c), dim3(256), 4 * TILE_BYTES, st, g,
                      MEpiWgrad{dw, K, accumulate, db, accumulate_db});
   return ovqa_check_launch("linear_bwd_weight(mfma)");
@@ -1430,10 +1439,12 @@ int mfma_grouped_wgrad(const ovqa_wgrad_problem* probs_dev, const int32_t* tiles
                        hipStream_t st) {
   if (n_tiles == 0) return OVQA_OK;
   if (direct_to_lds) {  // (every reduction length a multiple of 64)
+    OVQA_NOTE_LAUNCH((gemm_bf16_grouped_wgrad_glds_kernel<2>));
     hipLaunchKernelGGL((gemm_bf16_grouped_wgrad_glds_kernel<2>), dim3((unsigned)n_tiles), dim3(512), 4 * TILE_BYTES, st,
                        probs_dev, reinterpret_cast<const int4*>(tiles_dev));
     return ovqa_check_launch("grouped_linear_bwd_weight(mfma,glds)");
   }
+  OVQA_NOTE_LAUNCH(gemm_bf16_grouped_wgrad_kernel);
   hipLaunchKernelGGL(gemm_bf16_grouped_wgrad_kernel, dim3((unsigned)n_tiles), dim3(256), 4 * TILE_BYTES, st, probs_dev,
                      reinterpret_cast<const int4*>(tiles_dev));
   return ovqa_check_launch("grouped_linear_bwd_weight(mfma)");
@@ -1451,6 +1462,7 @@ int mfma_grouped_linear_bwd_weight_adam(const ovqa_wgrad_problem* probs_dev, con
     }
     attr = true;
   }
+  OVQA_NOTE_LAUNCH(gemm_bf16_grouped_wgrad_adam_kernel);
   hipLaunchKernelGGL(gemm_bf16_grouped_wgrad_adam_kernel, dim3((unsigned)n_tiles), dim3(512), 4 * TILE_BYTES, st, probs_dev,
                      reinterpret_cast<const int4*>(tiles_dev), targets_dev, consts);
   return ovqa_check_launch("grouped_linear_bwd_weight_adam(mfma,glds)");
@@ -1468,6 +1480,7 @@ int colsum_bf16(const void* dy, int64_t lddy, float* db, int64_t M, int64_t N, i
   int slabs = (int)((M + 63) / 64);
   if (slabs > 512) slabs = 512;
   const int rows_per_slab = (int)((M + slabs - 1) / slabs);
+  OVQA_NOTE_LAUNCH(colsum_bf16_kernel);
   hipLaunchKernelGGL(colsum_bf16_kernel, dim3(col_blocks, slabs), dim3(256), 0, st, (const bf16*)dy, lddy, db, (int)M,
                      (int)N, rows_per_slab);
   return ovqa_check_launch("colsum_bf16");

@@ -203,6 +203,9 @@ __device__ __forceinline__ void tile_e(const Args& g, int c0, int r0, Epi& epi, 
 #pragma unroll
           for (int i = 0; i < 4; i++) T256_MFMA(pf1, qf1, j, i);
         T256_PIN();
+        // this wave's own reads of stage kt (pf1[4..7] are first consumed after M) must have returned before M lets any wave
+        // request the DMA of stage kt + 2 into the same buffer: issued 48 MFMAs earlier, the wait costs nothing
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // M (the rotated waves have read stage kt by now)
         T256_PIN();
 #pragma unroll

@@ -54,6 +54,13 @@ def nerr(a, b):
     return ((a - b).abs().max() / max(1.0, b.abs().max().item())).item()
 
 
+def rel_max(a, ref):
+    """max |a - ref| / max |ref| (the reference's own scale, no floor)."""
+    a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
+    assert a.shape == ref.shape, (a.shape, ref.shape)
+    return ((a - ref).abs().max() / ref.abs().max()).item()
+
+
 def tol(dtype):
     return 1e-4 if dtype == F32 else 1e-2
 
@@ -188,16 +195,26 @@ def test_linear_fwd_strided_and_3d(dtype):
 def test_linear_fwd_256_tiles_grouped_raster_and_ragged_edges():
     """The 256 x 256-tile form (csrc/gemm_tile256.h): a grid large enough for the grouped tile order (>= 512 tiles, >= 8
     panels each way), and ragged edges in both dimensions (straight-line epilogue inside, guarded one on the edge tiles),
-    every epilogue, against fp32 products of the same bf16 operands."""
+    every epilogue, against fp32 products of the same bf16 operands.  The first three shapes (K < 1024) run the 128-tile
+    forms; the last two reach the 256-tile form itself (K >= 1024, >= 3/4 of a round of a 256-CU chip: plain raster with
+    ragged edges, and the grouped raster with a short last group, 588 tiles for the XCD remap, 17 K steps), which the
+    launch log must show."""
+    from openvivqa_amd import _lib
     o = ops()
-    for (M, N, K) in [(8192, 4096, 256), (6001, 2040, 320), (8000, 4104, 64)]:
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    for (M, N, K) in [(8192, 4096, 256), (6001, 2040, 320), (8000, 4104, 64), (6000, 2000, 1024), (12500, 3000, 1088)]:
         x, w = rnd(M, K, dtype=BF16), rnd(N, K, dtype=BF16, scale=K ** -0.5, seed=1)
         b, res = rnd(N, seed=2), rnd(M, N, dtype=BF16, seed=3)
         u = x.float() @ w.float().t() + b
+        _lib.launch_log_clear()
         assert nerr(o.linear_fwd(x, w, b), u) < 1e-2
+        if K >= 1024 and ncu == 256 and not FORCED_SIMPLE and os.environ.get("OVQA_GEMM_T256", "1") != "0":
+            assert _lib.launch_log() == ["ovqa_t256::kernel<MEpiBias,3>"], _lib.launch_log()
         y, pre = o.linear_fwd(x, w, b, o.EPI_BIAS_GELU, want_preact=True)
         assert nerr(pre, u) < 1e-2 and nerr(y, gelu(u.double())) < 1e-2
         assert nerr(o.linear_fwd(x, w, b, o.EPI_BIAS_RESIDUAL, residual=res), u + res.float()) < 1e-2
+    if ncu != 256:  # (the parity checks above ran; the 256-tile grid rule depends on the CU count)
+        pytest.skip(f"the 256-tile route of the K >= 1024 shapes is laid out for 256 CUs; this device has {ncu}: not checked")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16])
@@ -625,11 +642,14 @@ def test_grouped_transpose_and_dx_from_transposed_weights():
         a = o.linear_bwd_data(dy, w, addend=add)
         b = o.linear_bwd_data_wt(dy, wt, addend=add)
         assert nerr(b, a) < 6e-3  # identical on the MFMA path; one bf16 ulp (0.125 at ~25) when OVQA_FORCE_SIMPLE reroutes `a`
+        ref = dy.double() @ w.double() + add.double()  # and both against fp64 math: one bf16 rounding of the output
+        assert rel_max(b, ref) < 2 ** -8 and rel_max(a, ref) < 2 ** -8
         # column block: the middle 512 weight rows only (a strided [512, 512] view of wt)
         a = o.linear_bwd_data(dy[:, 512:1024].contiguous(), w[512:1024])
         blk = wt[:, 512:1024]
         b = o.linear_bwd_data_wt(dy[:, 512:1024], blk)
         assert nerr(b, a) < 6e-3  # identical on the MFMA path; one bf16 ulp (0.125 at ~25) when OVQA_FORCE_SIMPLE reroutes `a`
+        assert rel_max(b, dy[:, 512:1024].double() @ w[512:1024].double()) < 2 ** -8
         # FFN seam: dy [M, 512] x W2 [512, 2048] with dropout * gelu'(u)
         w2 = rnd(512, 2048, dtype=BF16, seed=6)
         w2t = w2.t().contiguous()
@@ -639,6 +659,8 @@ def test_grouped_transpose_and_dx_from_transposed_weights():
         a = o.linear_bwd_data(dyo, w2, preact=u, drop=drop)
         b = o.linear_bwd_data_wt(dyo, w2t, preact=u, drop=drop)
         assert nerr(b, a) < 6e-3  # identical on the MFMA path; one bf16 ulp (0.125 at ~25) when OVQA_FORCE_SIMPLE reroutes `a`
+        keep = o.dropout_keep_mask(drop, M * 2048, DEV).view(M, 2048).double() / 0.9
+        assert rel_max(b, (dyo.double() @ w2.double()) * keep * gelu_grad(u.double())) < 2 ** -8
 
 
 def test_layernorm_bwd_deferred_grouped_reduce():
@@ -1003,8 +1025,19 @@ def test_attention_q_fwd_equals_projection_plus_attention(dtype, B, nq, nk):
     """ovqa_attention_q_fwd (query projection inside the attention kernel; K / V already projected, as strided views of
     a packed buffer) against ovqa_linear_fwd + ovqa_attention_fwd: q bit-equal, o / lse within the kernels' tolerance,
     and the rounding residual o_lo written."""
+    _q_fwd_case(dtype, B, nq, nk, 8, 512)
+
+
+@pytest.mark.parametrize("B,nq,nk,H,Dm", [(3, 37, 20, 3, 768), (2, 100, 64, 5, 512), (4, 20, 100, 3, 512), (2, 65, 33, 6, 768)])
+def test_attention_q_fwd_odd_heads_and_wide_model(B, nq, nk, H, Dm):
+    """As above with an odd head count (one head per workgroup: attn_q_fwd_mfma_kernel<., 3, 1>) and d_model = 768 (the
+    entry point needs d_model % 64 == 0)."""
+    _q_fwd_case(BF16, B, nq, nk, H, Dm)
+
+
+def _q_fwd_case(dtype, B, nq, nk, H, Dm):
     o_ = ops()
-    H, d, Dm = 8, 64, 512
+    d = 64
     x = rnd(B, nq, Dm, dtype=dtype)
     w = rnd(H * d, Dm, dtype=dtype, scale=Dm ** -0.5, seed=1)
     b = rnd(H * d, seed=2)
@@ -1024,6 +1057,17 @@ def test_attention_q_fwd_equals_projection_plus_attention(dtype, B, nq, nk):
     assert nerr(o, o2) < tol(dtype) and nerr(lse, lse2) < 1e-3
     if dtype == BF16:
         assert len(lo) == 1 and nerr(o.float() + lo[0].float(), o2.float() + lo2[0].float()) < 2e-3
+    # fp64 math: the projection (one bf16 rounding + fp32 accumulation), the attention of the stored q (bf16 probabilities
+    # in P V: 2^-9 per term, bounded by P |V|), o + o_lo (the fp32 output: the probability term only)
+    qr = x.double() @ w.double().t() + b.double()
+    assert rel_max(q, qr) < (2 ** -8 if dtype == BF16 else 1e-5)
+    ro, rp, _ = att_ref(q, k, v, mask, H)
+    vh = v.double().view(B, nk, H, d).transpose(1, 2)
+    t = (rp @ vh.abs()).transpose(1, 2).reshape(B, nq, H * d).abs().max().item()
+    bar = 2 ** -8 * (ro.abs().max().item() + t) / ro.abs().max().item() if dtype == BF16 else 1e-4
+    assert rel_max(o, ro) < bar
+    if dtype == BF16:
+        assert rel_max(o.double() + lo[0].double(), ro) < bar
 
 
 @pytest.mark.parametrize("B,nq,nk", [(64, 100, 20), (3, 128, 32), (2, 65, 1), (5, 97, 13), (64, 20, 20), (3, 32, 32), (2, 1, 1),
@@ -1031,8 +1075,20 @@ def test_attention_q_fwd_equals_projection_plus_attention(dtype, B, nq, nk):
 def test_attention_bwd_do_equals_projection_plus_backward(B, nq, nk):
     """ovqa_attention_bwd_do (the fc_o dX product inside the guided-attention backward kernel, from the transposed weight
     copy) against ovqa_linear_bwd_data_wt + ovqa_attention_bwd: same dq, dk, dv."""
+    _bwd_do_case(B, nq, nk, 8, 512)
+
+
+@pytest.mark.parametrize("B,nq,nk,H,Dm", [(3, 100, 20, 3, 768), (2, 128, 100, 3, 512), (4, 20, 20, 6, 768),
+                                          (2, 70, 32, 5, 512)])
+def test_attention_bwd_do_odd_heads_and_wide_model(B, nq, nk, H, Dm):
+    """As above with odd head counts (guided and role-split forms; the single-tile form needs an even H) and d_model = 768
+    (the entry point needs d_model % 64 == 0)."""
+    _bwd_do_case(B, nq, nk, H, Dm)
+
+
+def _bwd_do_case(B, nq, nk, H, Dm):
     o_ = ops()
-    H, d, Dm = 8, 64, 512
+    d = 64
     q = rnd(B, nq, H * d, dtype=BF16)
     kv = rnd(B, nk, 4 * H * d, dtype=BF16, seed=1)  # packed K | V of two layers: slot 1 is ours
     k, v = kv[..., 2 * H * d:3 * H * d], kv[..., 3 * H * d:]
@@ -1042,8 +1098,8 @@ def test_attention_bwd_do_equals_projection_plus_backward(B, nq, nk):
     lo = []
     o, lse, _ = o_.attention_fwd(q, k, v, mask, H, lo_out=lo)
     dy = rnd(B, nq, Dm, dtype=BF16, seed=2)
-    group = rnd(Dm, 4 * Dm, dtype=BF16, scale=Dm ** -0.5, seed=3)  # transposed copies of an adjacency group [in, 4 x out]
-    wt = group[:, 3 * Dm:]                                          # fc_o's slice: rows = input features, strided
+    group = rnd(H * d, 4 * Dm, dtype=BF16, scale=Dm ** -0.5, seed=3)  # transposed copies of an adjacency group [in, 4 x out]
+    wt = group[:, 3 * Dm:]                                             # fc_o's slice: rows = input features, strided
     dkv1, dkv0 = torch.zeros_like(kv), torch.zeros_like(kv)
     fused_on = not FORCED_SIMPLE and not NO_FUSED_QKV
     # (round 5: 97-128 queries x 97-128 keys -- the image self-attention -- run the role-split backward with the projection
@@ -1062,6 +1118,16 @@ def test_attention_bwd_do_equals_projection_plus_backward(B, nq, nk):
                                  dv=dkv0[..., 3 * H * d:])
     rel = lambda a, b: ((a.double() - b.double()).norm() / b.double().norm()).item()
     assert rel(dq1, dq0) < 2e-3 and rel(dkv1, dkv0) < 2e-3, (rel(dq1, dq0), rel(dkv1, dkv0))
+    # fp64 autograd of the attention with dO = dy wt^T in fp64: relative L2 within two bf16 roundings of the inputs of the
+    # last products (dO, and dS / P~ before the MFMA) -- 2 x 2^-8
+    qd, kd, vd = (t.double().detach().clone().requires_grad_(True) for t in (q, k, v))
+    att_ref(qd, kd, vd, mask, H)[0].backward(dy.double() @ wt.double().t())
+    for got, ref in ((dq1, qd.grad), (dkv1[..., 2 * H * d:3 * H * d], kd.grad), (dkv1[..., 3 * H * d:], vd.grad)):
+        # (one key: softmax = 1 whatever the scores, dq = dk = 0 exactly; the kernel's cancellation residue is measured
+        # against the scale of dv, the gradient of the same magnitude of terms)
+        scale = ref if ref.double().norm() > 0 else vd.grad
+        e = ((got.double() - ref).norm() / scale.double().norm()).item()
+        assert e < 2 * 2 ** -8, e
 
 
 def test_model_end_entry_points_accept_empty_batches():
