@@ -350,9 +350,16 @@ int ovqa_attention_qkv_fwd(int dtype, const void* x, int64_t ldx, const void* w,
  * per sequence: decoders.py:46-63 under beam_search.py:41-62).  q [R, H*d] (row stride ldq), one query per row;
  * k / v: in-place caches, query row r reads cache row r / group (the `group` beams of a sample share the projected
  * encoder K / V; group = 1 for the self-attention caches), key j of that row at `kv_batch_stride * (r / group) +
- * j * ldk` (elements), `n` live keys (1 <= n <= 512); mask: additive fp32 [R, ldmask] or NULL; o [R, H*d].
+ * j * ldk` (elements), `n` live keys (1 <= n <= 2^30: key indices are 32-bit ints; no other bound); mask: additive
+ * FINITE fp32 [R, ldmask] or NULL (a fully masked row is uniform over its n keys); o [R, H*d].
  * d in {32, 64, 128}; pointers 16-byte aligned, ldq / ldk multiples of 16 bytes.  One wave per (row, head), K and V
- * streamed once: HBM-bound.  ovqa_last_dispatch() = "decode". */
+ * streamed once: HBM-bound.  Up to 512 keys a wave takes its keys in one pass (scores in a fixed LDS slot); longer key
+ * lists are walked in windows of that slot under an online softmax (running maximum, sum and output accumulators),
+ * results for n <= 512 being what they were before the windows existed, bit for bit.  `group` in 2 .. 8 (R a multiple
+ * of it): beams of a sample share a read of its K / V rows -- all of them, or a divisor of the group where that measured
+ * faster (5 .. 8 per read only from 64 keys on and with two workgroups per CU; past 512 keys at most 6) -- each query's
+ * result bit-identical to group = 1 on a gathered cache; any other group reads per row.
+ * ovqa_last_dispatch() = "decode". */
 int ovqa_attention_decode(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                           int64_t kv_batch_stride, int64_t group, const float* mask, int64_t ldmask,
                           void* o, int64_t ldo, int64_t R, int64_t H, int64_t n, int64_t d, float scale, void* stream);

@@ -523,10 +523,12 @@ int ovqa_attention_decode(int dtype, const void* q, int64_t ldq, const void* k, 
   OVQA_REQUIRE(ldq >= H * d && ldk >= H * d && ldv >= H * d && ldo >= H * d, OVQA_ERR_BAD_ARG,
                "attention_decode: row stride smaller than H*d");
   OVQA_REQUIRE(R * H <= 0x7fffffff, OVQA_ERR_UNSUPPORTED, "attention_decode: R*H too large");
+  OVQA_REQUIRE(n <= (1 << 30) && group <= 0x7fffffff, OVQA_ERR_UNSUPPORTED,
+               "attention_decode: n > 2^30 (key indices are 32-bit) or group too large");
   ovqa::AttnDecodeArgs a{q, k, v, ldq, ldk, ldv, kv_batch_stride, mask, ldmask, o, ldo,
                          (int)R, (int)H, (int)d, (int)n, (int)group, scale};
   OVQA_REQUIRE(ovqa::attention_decode_supported(a, dtype == OVQA_BF16 ? 2 : 4), OVQA_ERR_UNSUPPORTED,
-               "attention_decode: d must be 32 / 64 / 128, n <= 512, 16-byte aligned q / k / v rows");
+               "attention_decode: d must be 32 / 64 / 128, 16-byte aligned q / k / v / o rows");
   g_dispatch = "decode";
   return ovqa::attention_decode(dtype, a, as_stream(stream));
 }

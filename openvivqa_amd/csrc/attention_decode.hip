@@ -17,22 +17,37 @@
 
 namespace {
 
-constexpr int LMAX_KEYS = 512;  // scores of one wave and query live in LDS: 4 waves x G <= 4 queries x 2 KiB
+constexpr int LMAX_KEYS = 512;  // keys of ONE window: a wave's scores for one query live in a fixed LDS slot (512 floats,
+                                // 128 per wave in the split form); longer key lists are walked window by window
+constexpr int MAX_KEYS = 1 << 30;  // key indices (and a window's end, j + 16 * 4 passes) are 32-bit ints
 
 template <typename T> struct Vec16;  // 16 bytes of T
 template <> struct Vec16<bf16> { typedef bf16x8 type; static constexpr int N = 8; };
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
 
-// G = query rows per wave: the `group` beams of a sample (G = group <= 4: K and V of the sample's head are read ONCE for
-// all of them) or 1.  Scores: 4 lanes per key, 16 keys per pass; P.V: 16-byte chunks of a V row per lane, 64 / chunks
+// G = query rows per wave: beams of a sample (G divides group, G <= 8: K and V of the sample's head are read ONCE for
+// all of them; launch_decode picks it) or 1.  Scores: 4 lanes per key, 16 keys per pass; P.V: 16-byte chunks of a V row per lane, 64 / chunks
 // keys per pass, partial sums of the key groups reduced with xor shuffles at the end.
 // SPLIT = false: a wave owns a (row group, head) -- 4 independent problems per workgroup (short key lists: the
 // self-attention prefix).  SPLIT = true: the 4 waves of a workgroup share ONE (row group, head) and take a quarter of the
 // keys each (the 237 encoder positions: a lone wave streams its 60 KB at the latency of its own dependent round trips,
 // 28 us measured; four waves and twice the workgroups cut the chain to a quarter), partial softmaxes merged through LDS
 // (running maximum / sum, flash-decoding style).
-template <typename T, int D, int G, bool SPLIT>
+// WIN = false: the wave's keys fit its LDS slot (n <= 512), one pass: scores, softmax, P.V.  WIN = true (n > 512): the
+// wave walks its keys in windows of SLOT keys and carries a running maximum M, a running sum S and the UNNORMALISED
+// output accumulators across them (online softmax): a window's numerators are taken against max(M, window maximum),
+// and S and the accumulators are rescaled by exp(M_old - M_new) when the maximum rises (exp(-inf) = 0 before the first
+// window).  Masks are additive and FINITE, so a window of masked keys has a finite maximum and never poisons M; a wave
+// without keys runs no window and hands (-inf, 0, 0) to the merge.  The first V rows of window w + 1 are requested
+// before the softmax of window w starts, as the first window's are requested next to its K rows: one round trip per
+// window.  WIN is a separate instantiation so that the one-window form keeps its registers and its arithmetic.
+// G = 5 .. 8 exist in the SPLIT form only (LDS: 4 waves x 8 queries x 128 floats = 16 KiB) and keep fewer loads in
+// flight per lane (UK, UV below: batching of loads, not the order of any sum).
+template <typename T, int D, int G, bool SPLIT, bool WIN>
 __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a) {
+  static_assert(G <= 4 || SPLIT, "more than 4 queries per wave: split form only");
+  static_assert(!WIN || SPLIT, "past one window the four waves always share the problem");
+  static_assert(!WIN || G <= 6, "windowed forms of 7 and 8 queries measured slower than the forms they would replace");
   constexpr int SLOT = SPLIT ? LMAX_KEYS / 4 : LMAX_KEYS;  // scores a wave keeps per query
   __shared__ float sc[4][G][SLOT];
   __shared__ float red_m[4][G], red_s[4][G];
@@ -47,7 +62,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a
   // this wave's keys [j_lo, j_hi): everything, or a quarter rounded up to whole 16-key passes
   const int quarter = ((a.n + 3) / 4 + 15) & ~15;
   const int j_lo = SPLIT ? min(wave * quarter, a.n) : 0;
-  const int n = SPLIT ? min(j_lo + quarter, a.n) : a.n;  // j_hi
+  const int j_hi = SPLIT ? min(j_lo + quarter, a.n) : a.n;
   const int64_t kvrow = (int64_t)(r0 / a.group) * a.kv_batch_stride;
   const T* kb = (const T*)a.k + kvrow + h * D;
   const T* vb = (const T*)a.v + kvrow + h * D;
@@ -74,17 +89,29 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a
   constexpr int KG = 64 / CH;                  // keys in flight per pass
   static_assert(CH >= 1 && CH <= 64 && 64 % CH == 0, "chunks per row divide the wave");
   const int c = lane % CH, kg = lane / CH;
-  constexpr int UV = 8;  // V rows in flight per lane
+  constexpr int UV = G > 4 ? 4 : 8;  // V rows in flight per lane
   vec_t vpre[UV];
 #pragma unroll
   for (int u = 0; u < UV; u++)
-    vpre[u] = *reinterpret_cast<const vec_t*>(vb + (int64_t)min(j_lo + kg + KG * u, max(n - 1, 0)) * a.ldv + c * NV);
+    vpre[u] = *reinterpret_cast<const vec_t*>(vb + (int64_t)min(j_lo + kg + KG * u, max(j_hi - 1, 0)) * a.ldv + c * NV);
+  float inv[G], wmax[G];
+  float acc[G][NV];  // o = P V: lane -> 16-byte chunk c of key group kg
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    wmax[g] = -INFINITY;  // (WIN: the running maximum and the running sum)
+    inv[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; e++) acc[g][e] = 0.f;
+  }
+  // ---- the wave's windows [w0, n) of its keys [j_lo, j_hi): exactly one when !WIN
+  for (int w0 = j_lo; WIN ? w0 < j_hi : w0 == j_lo; w0 += SLOT) {
+  const int n = WIN ? min(w0 + SLOT, j_hi) : j_hi;
   // ---- scores: 16 keys per pass, every key row loaded once for the G queries
   float mx[G];
 #pragma unroll
   for (int g = 0; g < G; g++) mx[g] = -INFINITY;
-  constexpr int UK = 4;  // passes in flight: the loads of 64 keys are issued before the first dot product
-  for (int j0 = j_lo; j0 < n; j0 += 16 * UK) {
+  constexpr int UK = G > 4 ? 2 : 4;  // passes in flight: the loads of 64 keys are issued before the first dot product
+  for (int j0 = w0; j0 < n; j0 += 16 * UK) {
     vec_t kv[UK][NL];
     float mk[UK][G];  // the additive mask of these keys: requested with the K rows, not one dependent load per use
 #pragma unroll
@@ -116,39 +143,57 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a
         dot[g] += __shfl_xor(dot[g], 2, 64);
         if (j < n) {
           const float sv = dot[g] + mk[u][g];
-          if (part == 0) sc[wave][g][j - j_lo] = sv;
+          if (part == 0) sc[wave][g][j - w0] = sv;
           mx[g] = fmaxf(mx[g], sv);
         }
       }
     }
   }
+  // (WIN) the first V rows of the NEXT window: on their way while this window's softmax and P.V run
+  vec_t vnxt[WIN ? UV : 1];
+  if constexpr (WIN) {
+#pragma unroll
+    for (int u = 0; u < UV; u++)
+      vnxt[u] = *reinterpret_cast<const vec_t*>(vb + (int64_t)min(n + kg + KG * u, j_hi - 1) * a.ldv + c * NV);
+  }
   // ---- softmax numerators (the wave's own LDS rows: written and read by this wave only)
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the score stores of every lane have landed
   __builtin_amdgcn_wave_barrier();
-  float inv[G], wmax[G];
 #pragma unroll
   for (int g = 0; g < G; g++) {
-    const float m = wave_max(mx[g]);
+    float m = wave_max(mx[g]);
+    float resc = 0.f;
+    if constexpr (WIN) {  // against the running maximum; what was summed under the old one is scaled down to the new
+      m = fmaxf(m, wmax[g]);
+      resc = __expf(wmax[g] - m);  // (0 before the first window; 1 while the maximum stands)
+    }
     float sum = 0.f;
-    for (int j = j_lo + lane; j < n; j += 64) {
-      const float p = __expf(sc[wave][g][j - j_lo] - m);
-      sc[wave][g][j - j_lo] = p;
+    for (int j = w0 + lane; j < n; j += 64) {
+      const float p = __expf(sc[wave][g][j - w0] - m);
+      sc[wave][g][j - w0] = p;
       sum += p;
     }
     sum = wave_sum(sum);
     wmax[g] = m;
-    inv[g] = SPLIT ? sum : 1.f / sum;  // (split: the row sum itself, merged below)
+    if constexpr (WIN) {
+      inv[g] = fmaf(inv[g], resc, sum);
+#pragma unroll
+      for (int e = 0; e < NV; e++) acc[g][e] *= resc;
+    } else {
+      inv[g] = SPLIT ? sum : 1.f / sum;  // (split: the row sum itself, merged below)
+    }
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();
-  // ---- o = P V: lane -> 16-byte chunk c of key group kg
-  float acc[G][NV];
+  // ---- o += P V
+  if constexpr (!WIN) {
 #pragma unroll
-  for (int g = 0; g < G; g++)
+    for (int g = 0; g < G; g++)
 #pragma unroll
-    for (int e = 0; e < NV; e++) acc[g][e] = 0.f;
+      for (int e = 0; e < NV; e++) acc[g][e] = 0.f;
+  }
   bool first = true;
-  for (int j0 = j_lo + kg; j0 < n; j0 += KG * UV, first = false) {
+  for (int j0 = w0 + kg; j0 < n; j0 += KG * UV, first = false) {
     vec_t vv[UV];
     if (first) {  // (the first trip's rows are already here)
 #pragma unroll
@@ -164,13 +209,20 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a
       if (j < n) {
 #pragma unroll
         for (int g = 0; g < G; g++) {
-          const float p = sc[wave][g][j - j_lo];
+          const float p = sc[wave][g][j - w0];
 #pragma unroll
           for (int e = 0; e < NV; e++) acc[g][e] = fmaf(p, to_f32<T>(vv[u][e]), acc[g][e]);
         }
       }
     }
   }
+  if constexpr (WIN) {
+#pragma unroll
+    for (int u = 0; u < UV; u++) vpre[u] = vnxt[u];
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // this window's numerators are read before the next window's scores land on them
+    __builtin_amdgcn_wave_barrier();
+  }
+  }  // windows
 #pragma unroll
   for (int g = 0; g < G; g++) {
 #pragma unroll
@@ -307,33 +359,90 @@ int topk_rows(const float* x, int64_t ldx, int64_t R, int64_t V, int k, float* v
 
 bool attention_decode_supported(const AttnDecodeArgs& a, int esize) {
   const auto al = [&](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  return (a.d == 64 || a.d == 32 || a.d == 128) && a.n >= 1 && a.n <= LMAX_KEYS && a.group >= 1 && al(a.q) && al(a.k) &&
+  return (a.d == 64 || a.d == 32 || a.d == 128) && a.n >= 1 && a.n <= MAX_KEYS && a.group >= 1 && al(a.q) && al(a.k) &&
          al(a.v) && (a.ldq * esize) % 16 == 0 && (a.ldk * esize) % 16 == 0 && (a.ldv * esize) % 4 == 0 &&
          (a.ldv * esize) % 16 == 0 && (a.kv_batch_stride * esize) % 16 == 0 && (a.ldo * esize) % 16 == 0 && al(a.o);
 }
 
+#define OVQA_DEC(SPLITV, WINV)                                                                          \
+  do {                                                                                                  \
+    OVQA_NOTE_LAUNCH((attn_decode_kernel<T, D, G, SPLITV, WINV>));                                      \
+    hipLaunchKernelGGL((attn_decode_kernel<T, D, G, SPLITV, WINV>), grid, dim3(256), 0, st, a);         \
+  } while (0)
+template <typename T, int D, int G>
+static void launch_form(bool split, bool win, dim3 grid, const AttnDecodeArgs& a, hipStream_t st) {
+  if constexpr (G <= 4) {
+    if (!split) {
+      OVQA_DEC(false, false);
+      return;
+    }
+  }
+  if constexpr (G <= 6) {
+    if (win) {
+      OVQA_DEC(true, true);
+      return;
+    }
+  }
+  OVQA_DEC(true, false);
+}
+#undef OVQA_DEC
+
+static int device_cus() {
+  static int cus = -1;
+  if (cus < 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      cus = 256;
+  }
+  return cus;
+}
+
 template <typename T, int D>
 static int launch_decode(const AttnDecodeArgs& a, hipStream_t st) {
-  // G queries per wave: the beams of a sample share its K / V rows (group in {2, 3, 4} and R a multiple of it)
-  const int G = (a.group >= 2 && a.group <= 4 && a.R % a.group == 0) ? a.group : 1;
-  const int64_t problems = (int64_t)(a.R / G) * a.H;
   static int split_min = -1;
   if (split_min < 0) {
     const char* e = getenv("OVQA_DECODE_SPLIT_MIN");
     split_min = e ? atoi(e) : 64;
   }
-  const bool split = a.n >= split_min;  // long key lists: the four waves of a workgroup share one problem
-  const dim3 grid((unsigned)(split ? problems : (problems + 3) / 4)), block(256);
-#define OVQA_DEC(GV)                                                                              \
-  if (split) hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, true>), grid, block, 0, st, a);     \
-  else hipLaunchKernelGGL((attn_decode_kernel<T, D, GV, false>), grid, block, 0, st, a)
-  switch (G) {
-    case 2: OVQA_DEC(2); break;
-    case 3: OVQA_DEC(3); break;
-    case 4: OVQA_DEC(4); break;
-    default: OVQA_DEC(1);
+  const bool win = a.n > LMAX_KEYS;  // more keys than the waves' LDS slots: the windowed instantiation (split form only)
+  const bool split = win || a.n >= split_min;  // long key lists: the four waves of a workgroup share one problem
+  // G queries per wave: the beams of a sample share its K / V rows (group in 2 .. 8 and R a multiple of it): G is the
+  // largest divisor of the group that has a form here, so that the G rows of a wave belong to one sample (group 8 past
+  // 512 keys runs as two waves of 4).  The forms of 5 .. 8 queries (every choice MEASURED):
+  //   * exist in the split form only (LDS), i.e. from OVQA_DECODE_SPLIT_MIN keys on;
+  //   * are taken only where they still put two workgroups on every CU: a wave's time is its chain of round trips plus
+  //     G dot products per key, so with CUs to spare more workgroups of fewer queries win (B = 32: 256 workgroups of 5
+  //     lose to 1280 of 1, whose re-reads of a sample's rows hit in L2; B = 64 wins);
+  //   * windowed (n > 512) stop at 6: 7 and 8 queries need every VGPR plus AGPR copies at one wave per SIMD and measured
+  //     no faster than per-row reads (7) and slower than two waves of 4 (8).
+  // Past 8 beams, or R not a multiple of the group, every row reads for itself.  Same bits whichever form runs.
+  static int group_max = -1;
+  if (group_max < 0) {
+    const char* e = getenv("OVQA_DECODE_GROUP_MAX");  // (A/B: 4 = the forms before groups of 5 .. 8, 1 = no sharing)
+    group_max = e ? atoi(e) : 8;
   }
-#undef OVQA_DEC
+  int G = 1;
+  if (a.group >= 2 && a.group <= 8 && a.R % a.group == 0) {
+    // the largest divisor of the group that has a form: the G rows of a wave then belong to one sample
+    for (int g = a.group; g > 1; g--) {
+      if (a.group % g != 0 || g > group_max) continue;
+      if (g > 4 && (!split || (int64_t)(a.R / g) * a.H < 2 * (int64_t)device_cus() || (win && g > 6))) continue;
+      G = g;
+      break;
+    }
+  }
+  const int64_t problems = (int64_t)(a.R / G) * a.H;
+  const dim3 grid((unsigned)(split ? problems : (problems + 3) / 4));
+  switch (G) {
+    case 2: launch_form<T, D, 2>(split, win, grid, a, st); break;
+    case 3: launch_form<T, D, 3>(split, win, grid, a, st); break;
+    case 4: launch_form<T, D, 4>(split, win, grid, a, st); break;
+    case 5: launch_form<T, D, 5>(split, win, grid, a, st); break;
+    case 6: launch_form<T, D, 6>(split, win, grid, a, st); break;
+    case 7: launch_form<T, D, 7>(split, win, grid, a, st); break;
+    case 8: launch_form<T, D, 8>(split, win, grid, a, st); break;
+    default: launch_form<T, D, 1>(split, win, grid, a, st);
+  }
   return ovqa_check_launch("attention_decode");
 }
 
