@@ -71,8 +71,9 @@ const char* ovqa_last_dispatch(void);
  * as "<kernel expression at the launch site> @ <__PRETTY_FUNCTION__ of the launching function>" -- the second part's
  * [NAME = value, ...] bindings give the template arguments the first leaves symbolic -- or NULL past the end.  The
  * returned text is valid until the next ovqa_launch_log call on the thread.  The first 256 launches are kept.  Every
- * launch of the MFMA GEMM and attention kernels is logged (timed or not); recording is a host-side pointer store (no
- * device work, no synchronisation, safe under stream capture). */
+ * launch of the MFMA GEMM and attention kernels, of the weight-gradient, bias-gradient and LayerNorm partial-reduce kernels
+ * and of the Adam kernels is logged (timed or not); recording is a host-side pointer store (no device work, no
+ * synchronisation, safe under stream capture). */
 void ovqa_launch_log_clear(void);
 const char* ovqa_launch_log(int i);
 /* Launch timing (diagnostic, used by bench.py's roofline figure).  Between ovqa_launch_timing_begin(max) and

@@ -1476,6 +1476,7 @@ int colsum_bf16(const void* dy, int64_t lddy, float* db, int64_t M, int64_t N, i
       return OVQA_ERR_LAUNCH;
     }
   }
+  if (M == 0) return OVQA_OK;  // (no rows: db is zero, or what it was under accumulate; no slab to divide the rows by)
   const int col_blocks = (int)((N / 8 + 63) / 64);
   int slabs = (int)((M + 63) / 64);
   if (slabs > 512) slabs = 512;

@@ -411,6 +411,7 @@ int bwd_dispatch(const void* dy, const void* x, const float* gamma, const float*
   if (rc != OVQA_OK) return rc;
   if (dgamma == nullptr && dbeta == nullptr) return OVQA_OK;  // partials stay in ws (deferred grouped reduce)
   const ovqa_reduce_problem pr{partial, dgamma, dbeta, nblocks, (int32_t)D, accumulate ? 1 : 0, 0};
+  OVQA_NOTE_LAUNCH(ln_bwd_reduce_kernel);
   hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)((2 * D + 255) / 256)), dim3(512), 0, st, pr);
   return ovqa_check_launch("layernorm_bwd_reduce");
 }
@@ -457,6 +458,7 @@ int grouped_partial_reduce(const ovqa_reduce_problem* probs, int n, int max_bloc
   if (n <= 0) return OVQA_OK;
   (void)max_blocks;  // (a workgroup walks all partial rows of its columns: the grid no longer depends on their number)
   dim3 grid((unsigned)((2 * max_D + 255) / 256), 1u, (unsigned)n);
+  OVQA_NOTE_LAUNCH(ln_bwd_grouped_reduce_kernel);
   hipLaunchKernelGGL(ln_bwd_grouped_reduce_kernel, grid, dim3(512), 0, st, probs);
   return ovqa_check_launch("grouped_partial_reduce");
 }

@@ -325,12 +325,15 @@ int adam_step(float* param, const void* grad, int grad_dtype, float* m, float* v
   OVQA_REQUIRE(((uintptr_t)param % 16 == 0) && ((uintptr_t)grad % 8 == 0) && ((uintptr_t)m % 16 == 0) &&
                    ((uintptr_t)v % 16 == 0) && (shadow == nullptr || (uintptr_t)shadow % 8 == 0),
                OVQA_ERR_BAD_ARG, "adam_step: arena pointers must be 16-byte aligned");
-  if (grad_dtype == OVQA_BF16)
+  if (grad_dtype == OVQA_BF16) {
+    OVQA_NOTE_LAUNCH(adam_kernel<bf16>);
     hipLaunchKernelGGL(adam_kernel<bf16>, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, st, param, (const bf16*)grad, m, v,
                        (bf16*)shadow, n, lr, lr_scale_ptr, b1, b2, eps, wd, grad_scale, step_ptr);
-  else
+  } else {
+    OVQA_NOTE_LAUNCH(adam_kernel<float>);
     hipLaunchKernelGGL(adam_kernel<float>, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, st, param, (const float*)grad, m,
                        v, (bf16*)shadow, n, lr, lr_scale_ptr, b1, b2, eps, wd, grad_scale, step_ptr);
+  }
   return ovqa_check_launch("adam_step");
 }
 
@@ -343,14 +346,17 @@ int adam_step_tiled(float* param, const void* grad, int grad_dtype, float* m, fl
   if (flat_blocks > 64) flat_blocks = 64;
   if (n_tiles + flat_blocks == 0) return OVQA_OK;
   const dim3 grid((unsigned)(n_tiles + flat_blocks));
-  if (grad_dtype == OVQA_BF16)
+  if (grad_dtype == OVQA_BF16) {
+    OVQA_NOTE_LAUNCH(adam_tiled_kernel<bf16>);
     hipLaunchKernelGGL(adam_tiled_kernel<bf16>, grid, dim3(256), 0, st, param, (const bf16*)grad, m, v, (bf16*)shadow,
                        (bf16*)shadow_t, tiles, n_tiles, flat_lo, flat_hi, lr, lr_scale_ptr, b1, b2, eps, wd, grad_scale,
                        step_ptr);
-  else
+  } else {
+    OVQA_NOTE_LAUNCH(adam_tiled_kernel<float>);
     hipLaunchKernelGGL(adam_tiled_kernel<float>, grid, dim3(256), 0, st, param, (const float*)grad, m, v, (bf16*)shadow,
                        (bf16*)shadow_t, tiles, n_tiles, flat_lo, flat_hi, lr, lr_scale_ptr, b1, b2, eps, wd, grad_scale,
                        step_ptr);
+  }
   return ovqa_check_launch("adam_step_tiled");
 }
 

@@ -407,21 +407,14 @@ class WgradQueue:
         if capturing:
             self.keepalive.append((host, devbuf, red))
 
-    def flush(self, final=False):
-        """Launch everything queued so far.  ``final``: the last launch of the pass (``finish``): the one that may carry the
-        optimiser step (``self.adam``)."""
-        if not self.items:
-            return
+    @classmethod
+    def tile_table(cls, shapes):
+        """The tile table of one grouped launch over problems of ``shapes`` [(M, N, K)]: int32 [n, 4] rows {problem, tile over
+        N, tile over K, 0} in units of TILE, n a multiple of 8, rows of -1 = padding (the workgroup returns).  Every tile of
+        every problem occurs once."""
         import numpy as np
-        items, self.items = self.items, []
-        dev = items[0][0].device
-        probs = (_lib.WgradProblem * len(items))()
-        per_problem = []
-        fast = all(it[5] % 64 == 0 and it[3] % 8 == 0 and it[4] % 8 == 0 and it[0].data_ptr() % 16 == 0
-                   and it[1].data_ptr() % 16 == 0 for it in items)
-        tile = self.TILE
-        for i, (dy, x, dw, lddy, ldx, M, N, K, acc, db) in enumerate(items):
-            probs[i] = _lib.WgradProblem(_p(dy), _p(x), _p(dw), _p(db), lddy, ldx, M, N, K, acc)
+        tile, per_problem = cls.TILE, []
+        for i, (M, N, K) in enumerate(shapes):
             tn, tk = (N + tile - 1) // tile, (K + tile - 1) // tile
             per_problem.append((M * tn * tk, M, [(i, c, r, 0) for c in range(tn) for r in range(tk)]))
         # XCD-aware order: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD
@@ -456,27 +449,50 @@ class WgradQueue:
         for xcd, b in enumerate(bins):
             if b[1]:
                 tile_arr[xcd:xcd + 8 * len(b[1]):8] = np.array(b[1], dtype=np.int32)
+        return tile_arr
+
+    @staticmethod
+    def table_image(prob_bytes, tile_arr, target_bytes=None):
+        """The host image of one launch's device tables: the problem array, the int4 tile table behind it at the next
+        16-byte boundary and (optionally) one Adam target per problem behind that, again 16-byte aligned.  Returns (uint8
+        array, offset of the tile table, offset of the targets)."""
+        import numpy as np
+        tiles_off = len(prob_bytes) + ((-len(prob_bytes)) % 16)
+        targets_off = tiles_off + tile_arr.nbytes + ((-tile_arr.nbytes) % 16)
+        image = np.zeros(targets_off + (len(target_bytes) if target_bytes is not None else 0), dtype=np.uint8)
+        image[:len(prob_bytes)] = np.frombuffer(prob_bytes, dtype=np.uint8)
+        image[tiles_off:tiles_off + tile_arr.nbytes] = np.ascontiguousarray(tile_arr).view(np.uint8).reshape(-1)
+        if target_bytes is not None:
+            image[targets_off:] = np.frombuffer(target_bytes, dtype=np.uint8)
+        return image, tiles_off, targets_off
+
+    def flush(self, final=False):
+        """Launch everything queued so far.  ``final``: the last launch of the pass (``finish``): the one that may carry the
+        optimiser step (``self.adam``)."""
+        if not self.items:
+            return
+        items, self.items = self.items, []
+        dev = items[0][0].device
+        probs = (_lib.WgradProblem * len(items))()
+        fast = all(it[5] % 64 == 0 and it[3] % 8 == 0 and it[4] % 8 == 0 and it[0].data_ptr() % 16 == 0
+                   and it[1].data_ptr() % 16 == 0 for it in items)
+        for i, (dy, x, dw, lddy, ldx, M, N, K, acc, db) in enumerate(items):
+            probs[i] = _lib.WgradProblem(_p(dy), _p(x), _p(dw), _p(db), lddy, ldx, M, N, K, acc)
+        tile_arr = self.tile_table([(it[5], it[6], it[7]) for it in items])
         tiles = tile_arr
-        prob_bytes = np.frombuffer(bytes(probs), dtype=np.uint8)
-        pad = (-prob_bytes.size) % 16  # keep the int4 tile table 16-byte aligned
-        if pad:
-            prob_bytes = np.concatenate([prob_bytes, np.zeros(pad, dtype=np.uint8)])
         # the optimiser step inside this launch (the last one of the pass): one target per problem behind the tile table
         targets = None
         if final and self.adam is not None and fast and os.environ.get("OVQA_FORCE_SIMPLE", "0") in ("", "0"):
             tl = self.adam.targets(items)
             if any(t is not None for t in tl):
                 arr = (_lib.AdamTarget * len(items))(*[t if t is not None else _lib.AdamTarget() for t in tl])
-                targets = np.frombuffer(bytes(arr), dtype=np.uint8)
-        tile_bytes = tile_arr.nbytes + ((-tile_arr.nbytes) % 16)
-        nbytes = prob_bytes.size + tile_bytes + (targets.size if targets is not None else 0)
+                targets = bytes(arr)
+        image, tiles_off, targets_off = self.table_image(bytes(probs), tile_arr, targets)
+        nbytes = image.size
         capturing = torch.cuda.is_current_stream_capturing()
         entry = self._buffers(nbytes, dev, capturing)
         host, devbuf = entry[0], entry[1]
-        host[:prob_bytes.size] = torch.from_numpy(prob_bytes.copy())
-        host[prob_bytes.size:prob_bytes.size + tile_arr.nbytes] = torch.from_numpy(tile_arr.view(np.uint8).reshape(-1).copy())
-        if targets is not None:
-            host[prob_bytes.size + tile_bytes:nbytes] = torch.from_numpy(targets.copy())
+        host[:nbytes] = torch.from_numpy(image)
         # (on the main stream: a fork / join in a captured graph turns every node boundary of the replay into a cross-queue
         # dependency -- scripts/boundary_bench.py: 1.6 us per dependent launch on one queue)
         main = torch.cuda.current_stream(dev)
@@ -484,12 +500,12 @@ class WgradQueue:
         if targets is not None:
             consts = self.adam.consts()
             _lib.check(_lib.load().ovqa_grouped_linear_bwd_weight_adam(
-                OVQA_BF16, devbuf.data_ptr(), devbuf.data_ptr() + prob_bytes.size, len(tiles),
-                devbuf.data_ptr() + prob_bytes.size + tile_bytes, C.addressof(consts), main.cuda_stream),
+                OVQA_BF16, devbuf.data_ptr(), devbuf.data_ptr() + tiles_off, len(tiles),
+                devbuf.data_ptr() + targets_off, C.addressof(consts), main.cuda_stream),
                 "grouped_linear_bwd_weight_adam")
         else:
             _lib.check(_lib.load().ovqa_grouped_linear_bwd_weight(
-                OVQA_BF16, devbuf.data_ptr(), devbuf.data_ptr() + prob_bytes.size, len(tiles), int(fast),
+                OVQA_BF16, devbuf.data_ptr(), devbuf.data_ptr() + tiles_off, len(tiles), int(fast),
                 main.cuda_stream), "grouped_linear_bwd_weight")
         self._used(entry, main, capturing)
         self.inflight.append(items)
