@@ -60,8 +60,19 @@ extern "C" int ovqa_debug_probe_gemm(unsigned long long* out) {
 extern "C" int ovqa_debug_probe_gemm_wgs(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_probe_wg), sizeof(unsigned long long) * 4 * (size_t)n);
 }
+// timeline of every workgroup of the last fused dW + Adam launch: {start, K loop done, state loads issued, last state
+// store issued, end, HW_ID | XCC_ID << 32, -, -} (scripts/wgrad_adam_timeline.py); all zero for unfused and padding entries
+__device__ unsigned long long g_probe_adam[4096][8];
+#define OVQA_APROBE(i)                                                                   \
+  do {                                                                                   \
+    if (threadIdx.x == 0 && blockIdx.x < 4096) g_probe_adam[blockIdx.x][i] = wall_clock64(); \
+  } while (0)
+extern "C" int ovqa_debug_probe_wgrad_adam(unsigned long long* out, int n) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_probe_adam), sizeof(unsigned long long) * 8 * (size_t)n);
+}
 #else
 #define OVQA_GPROBE(i) do {} while (0)
+#define OVQA_APROBE(i) do {} while (0)
 #endif
 
 namespace {
@@ -320,6 +331,14 @@ __device__ __forceinline__ void stage_glds_piece(char* tile, const bf16* __restr
                                    (lds_void*)(tile + ci * 1024), 16, 0, 0);
 }
 
+// Epilogue hook inside the LAST K step of gemm_tile_glds (behind its wait and barrier, in front of its MFMAs): the first
+// point from which a load of the epilogue's own is not waited for by a later K step (the vector-memory counter is in
+// order and a ring of two waits for vmcnt(0) in every step).  Epilogues without a last_k_step() compile to nothing.
+template <typename Epi>
+__device__ __forceinline__ auto epi_last_k_step(Epi& epi, int) -> decltype(epi.last_k_step(), void()) { epi.last_k_step(); }
+template <typename Epi>
+__device__ __forceinline__ void epi_last_k_step(Epi&, long) {}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
@@ -416,6 +435,7 @@ __device__ __forceinline__ void gemm_tile_glds(const GemmArgs& g, int c0, int r0
     }
     __builtin_amdgcn_s_barrier();
     if (kt + NBUF - 1 < nkt) issue(kt + NBUF - 1);
+    if (kt == nkt - 1) epi_last_k_step(epi, 0);
     const char* Ps = smem + (kt % NBUF) * STAGE;
     const char* Qs = Ps + PT_BYTES;
 #pragma unroll
@@ -924,37 +944,174 @@ __global__ __launch_bounds__(512, 4) void gemm_bf16_grouped_wgrad_glds_kernel(co
   gemm_tile_glds<true, true, MEpiWgrad, true, NBUF, 8, 128, 128>(g, t.y * BT, t.z * BT, epi, smem);
 }
 
-// ---- the optimiser step inside the grouped dW (round 5) -------------------------------------------------------------------
+// ---- the optimiser step inside the grouped dW (round 5; tail reworked later) -----------------------------------------------
 // For a weight whose gradient is exactly one product of the step (and no exchange between ranks follows), the workgroup
 // that finished a 128 x 128 tile of dW applies Adam to that tile right away: the fp32 tile goes to LDS (the ring is idle
-// after the K loop; 16-byte chunks XOR-swizzled by the row so that the fragment stores -- 16 rows of one chunk column per
-// wave instruction -- and the row-wise reads are both conflict free), every thread then owns 16-byte pieces of whole rows:
-// master, both moments in and out (512-byte row segments per 32 lanes, streaming cache policy like the tiled Adam kernel),
-// the bf16 shadow out, its bf16 values back into LDS, and after a barrier the tile of the TRANSPOSED shadow is gathered
-// from there (8 output features per 16-byte store).  The gradient never reaches HBM (8 B per weight of traffic less) and
-// the optimiser state is streamed while other workgroups' K loops keep the fetch path busy with L2 hits.
-// Same update function as adam_tiled_kernel (common.h): same bits.
+// after the K loop), every thread then owns 16-byte pieces of whole rows: master, both moments in and out (512-byte row
+// segments per 32 lanes, streaming cache policy like the tiled Adam kernel), the bf16 shadow out, its bf16 values back
+// into LDS, and after a barrier the tile of the TRANSPOSED shadow is gathered from there (8 output features per 16-byte
+// store).  The gradient never reaches HBM (8 B per weight of traffic less) and the optimiser state is streamed while other
+// workgroups' K loops keep the fetch path busy with L2 hits.  Same update function as adam_tiled_kernel (common.h): same
+// bits.
+//   * LDS image: 128 rows (output feature ln) of 32 sixteen-byte chunks (4 input features li), chunk index XOR-ed with
+//     adam_tile_swz(ln) = ln ^ (ln >> 3).  The `ln` term spreads the fragment stores (8 consecutive rows of one chunk column)
+//     and keeps a row's 8-lane reads on 8 adjacent chunks; the `ln >> 3` term spreads the transposed gather, whose 64 lanes
+//     read rows 8 j + e (j = lane & 15) of one chunk column: with `ln` alone (as this tail was first written) those rows fall
+//     on 2 of the 16 chunk positions of a bank row -- 8 distinct dwords per bank, SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE =
+//     0.22 in the step; 0.03 now.  The three patterns are pinned below by static_asserts over a 64-bank model.  (The counter
+//     follows per-instruction banking -- 32 banks per half wave for the 2-byte reads and the 8-byte write-back -- under
+//     which the gather and the write-back are still 2-way: profiles/README.md has the arithmetic and the remedy.)
+//   * The optimiser state of a tile is fetched in ONE round trip: the loads of the first kHoist passes are issued inside the
+//     last K step (epi_last_k_step: any earlier and the next K step's vmcnt(0) would wait for them), so that the last MFMAs,
+//     the accumulator dump and its barriers run under the HBM latency; the loads of the other passes follow the dump (their
+//     registers are the accumulators' until then), all of them in front of the first update.  Before, the update loop
+//     fetched two passes at a time: four dependent round trips per tile, the first one started behind the barriers.
+constexpr int adam_tile_swz(int ln) { return (ln ^ (ln >> 3)) & 31; }
+// float index of the 16-byte chunk that holds input features li & ~3 .. of output feature ln (both tile-relative)
+constexpr int adam_tile_chunk(int ln, int li) { return ln * 128 + ((((li >> 2) ^ adam_tile_swz(ln)) & 31) << 2); }
+// row-wise pass: thread tid owns chunk tid & 31 of row pass * 16 + (tid >> 5)
+constexpr int adam_row_of(int pass, int tid) { return pass * 16 + (tid >> 5); }
+// transposed gather: thread tid builds 8 consecutive output features gather_ln0 .. + 7 of input feature gather_li
+constexpr int adam_gather_li(int pass, int tid) { return pass * 32 + (tid >> 4); }
+constexpr int adam_gather_ln0(int tid) { return (tid & 15) * 8; }
+
+// 64-bank LDS model (bank = dword address mod 64): the cost of a group of lanes that the LDS serves together is the largest
+// number of DISTINCT dwords they address on one bank (1 = conflict free).  `bytes` per lane: 2 (one dword) or 16 (four).
+struct LdsBankModel {
+  int dword[64][8] = {};
+  int n[64] = {};
+  constexpr void touch(int byte_addr, int bytes) {
+    for (int d = byte_addr >> 2; d <= (byte_addr + bytes - 1) >> 2; d++) {
+      const int b = d & 63;
+      bool seen = false;
+      for (int k = 0; k < n[b]; k++) seen = seen || dword[b][k] == d;
+      if (!seen && n[b] < 8) dword[b][n[b]++] = d;
+    }
+  }
+  constexpr int cost() const {
+    int worst = 0;
+    for (int b = 0; b < 64; b++) worst = n[b] > worst ? n[b] : worst;
+    return worst;
+  }
+};
+template <typename Chunk>
+constexpr int adam_tile_worst_cost(Chunk chunk) {
+  int worst = 0;
+  // accumulator dump: a 16-byte store per lane; 8 lanes (8 consecutive rows of one chunk column) are served together
+  for (int col = 0; col < 32; col++)
+    for (int r8 = 0; r8 < 128; r8 += 8) {
+      LdsBankModel m;
+      for (int l = 0; l < 8; l++) m.touch(chunk(r8 + l, col * 4) * 4, 16);
+      worst = m.cost() > worst ? m.cost() : worst;
+    }
+  // row-wise reads (and the bf16 write-back into the same slots): 8 lanes read 8 neighbouring chunks of one row
+  for (int pass = 0; pass < 8; pass++)
+    for (int t8 = 0; t8 < 512; t8 += 8) {
+      LdsBankModel m;
+      for (int l = 0; l < 8; l++) m.touch(chunk(adam_row_of(pass, t8 + l), ((t8 + l) & 31) * 4) * 4, 16);
+      worst = m.cost() > worst ? m.cost() : worst;
+    }
+  // transposed gather: one 2-byte read per lane, the whole wave at once, for each of the 8 elements of the output piece
+  for (int pass = 0; pass < 4; pass++)
+    for (int w = 0; w < 8; w++)
+      for (int e = 0; e < 8; e++) {
+        LdsBankModel m;
+        for (int l = 0; l < 64; l++) {
+          const int tid = w * 64 + l, li = adam_gather_li(pass, tid);
+          m.touch(chunk(adam_gather_ln0(tid) + e, li) * 4 + 2 * (li & 3), 2);
+        }
+        worst = m.cost() > worst ? m.cost() : worst;
+      }
+  return worst;
+}
+constexpr int adam_tile_chunk_round5(int ln, int li) { return ln * 128 + ((((li >> 2) ^ ln) & 31) << 2); }
+static_assert(adam_tile_worst_cost(adam_tile_chunk) == 1,
+              "fused dW + Adam tail: the LDS image must keep the dump, the row-wise reads and the transposed gather conflict free");
+static_assert(adam_tile_worst_cost(adam_tile_chunk_round5) == 8, "the bank model must see the 8-way gather conflict of the first swizzle");
+
+// (global address space, not generic: a flat load counts on lgkmcnt too, and the K step's hand-placed lgkmcnt(0) in front of
+// its MFMAs would then wait for the state)
+typedef __attribute__((address_space(1))) f32x4 gbl_f32x4;
+typedef __attribute__((address_space(1))) bf16x4 gbl_bf16x4;
+typedef __attribute__((address_space(1))) char gbl_char;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) u32x4 gbl_u32x4;
+// Workgroup barrier that orders LDS accesses only.  __syncthreads() also releases global memory: on gfx9 that is a
+// vmcnt(0) in front of the barrier, i.e. a wait for every state load and store in flight.
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// LDS reads the compiler does not see (as frag_tr_nowait's): a read it sees waits for vmcnt(0) first -- the K loop's
+// direct-to-LDS loads might still be writing, for all it knows -- and with that for every state load and store in flight.
+// The caller waits for lgkmcnt(0) by hand.
+__device__ __forceinline__ f32x4 lds_read16_nowait(uint32_t addr) {
+  f32x4 v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  return v;
+}
+// (zero-extended; not the d16 / d16_hi pair into one register: with SRAM ECC a d16 read clears the other half)
+__device__ __forceinline__ uint32_t lds_read_u16_nowait(uint32_t addr) {
+  uint32_t v;
+  asm volatile("ds_read_u16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  return v;
+}
 struct MEpiWgradAdam {
   static constexpr bool kWide = false, kTwoPhase = false;
+  static constexpr int kPasses = 8;  // row-wise passes over the tile: 16 rows each
+  static constexpr int kHoist = 2;   // passes whose state loads are issued inside the last K step
+  static constexpr int kFlight = 7;  // passes whose state is in flight (or in registers) at once (8: spills)
   float* dw; int64_t ld; int accumulate; float* db; int accumulate_db;
   float* tile;  // fused: the fp32 tile in LDS; nullptr: the plain gradient store
   int c0, r0;
+  gbl_f32x4 *param, *exp_avg, *exp_avg_sq;  // the fused target's state (all nullptr when tile is)
+  f32x4 hp[kHoist], hm[kHoist], hv[kHoist];   // ... of this thread's pieces of the first kHoist passes
+  // A thread's piece of a pass in the row-major arrays: the tile's first piece (workgroup-uniform index in 16-byte pieces;
+  // K % 128 == 0: 16-byte aligned) plus a 32-bit byte offset per thread and pass that serves all arrays (scalar base + vector
+  // offset addressing: one address register per pass instead of two per load and store; 128 rows of K floats stay below
+  // 2^32 bytes for K < 2^23).  (Folding the pass into the scalar base was tried: the compiler re-associates it into 64-bit
+  // vector addresses and spills.)
+  __device__ __forceinline__ int64_t tile_piece() const { return ((int64_t)c0 * ld + r0) >> 2; }
+  __device__ __forceinline__ uint32_t piece_off(int pass) const {
+    const uint32_t tid = threadIdx.x;
+    return ((uint32_t)adam_row_of(pass, tid) * (uint32_t)ld + (tid & 31) * 4) * 4;
+  }
+  template <typename T>
+  __device__ __forceinline__ static T* at(T* tile_base, uint32_t off) { return (T*)((gbl_char*)tile_base + off); }
+  __device__ __forceinline__ void load_pass(int pass, f32x4& p, f32x4& m, f32x4& v) const {
+    const int64_t t4 = tile_piece();
+    const uint32_t off = piece_off(pass);
+    p = __builtin_nontemporal_load(at(param + t4, off));
+    m = __builtin_nontemporal_load(at(exp_avg + t4, off));
+    v = __builtin_nontemporal_load(at(exp_avg_sq + t4, off));
+  }
+  __device__ __forceinline__ void last_k_step() {
+    if (!tile) return;  // (workgroup-uniform) an unfused problem's target is all NULL
+#pragma unroll
+    for (int pass = 0; pass < kHoist; pass++) load_pass(pass, hp[pass], hm[pass], hv[pass]);
+  }
   __device__ __forceinline__ void init() {
-    if (tile) __syncthreads();  // (workgroup-uniform) every wave is done with the last K tile's fragments
+    OVQA_APROBE(1);
+    if (tile) lds_barrier();  // (workgroup-uniform) every wave is done with the last K tile's fragments
   }
   __device__ __forceinline__ bool wants_colsum() const { return db != nullptr; }
-  __device__ __forceinline__ void colsum(int n, float v) const { db[n] = accumulate_db ? db[n] + v : v; }
+  // (the unfused problems' accesses are global ones too: after a FLAT access on any path into the tail the compiler waits
+  // for vmcnt(0) at the first use of a loaded register, whatever was issued behind that load)
+  __device__ __forceinline__ void colsum(int n, float v) const {
+    __attribute__((address_space(1))) float* d = (__attribute__((address_space(1))) float*)db;
+    d[n] = accumulate_db ? d[n] + v : v;
+  }
   __device__ __forceinline__ void operator()(int n, int i, const f32x4& a) const {
     if (tile) {
-      const int ln = n - c0, li = i - r0;
-      *reinterpret_cast<f32x4*>(tile + ln * 128 + ((((li >> 2) ^ ln) & 31) << 2)) = a;
+      *reinterpret_cast<f32x4*>(tile + adam_tile_chunk(n - c0, i - r0)) = a;
       return;
     }
-    float4* p = reinterpret_cast<float4*>(dw + (int64_t)n * ld + i);
-    float4 v = make_float4(a[0], a[1], a[2], a[3]);
+    gbl_f32x4* p = (gbl_f32x4*)(dw + (int64_t)n * ld + i);
+    f32x4 v = a;
     if (accumulate) {
-      const float4 o = *p;
-      v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
+      const f32x4 o = *p;
+      v[0] += o[0]; v[1] += o[1]; v[2] += o[2]; v[3] += o[3];
     }
     *p = v;
   }
@@ -972,50 +1129,84 @@ __global__ __launch_bounds__(512, 4) void gemm_bf16_grouped_wgrad_adam_kernel(co
   const bool fused = tg.param != nullptr;  // (workgroup-uniform)
   const int c0 = t.y * BT, r0 = t.z * BT;
   float* T = reinterpret_cast<float*>(smem);
-  MEpiWgradAdam epi{pr.dw, pr.K, pr.accumulate & 1, pr.db, (pr.accumulate >> 1) & 1, fused ? T : nullptr, c0, r0};
+  constexpr int NP = MEpiWgradAdam::kPasses, NH = MEpiWgradAdam::kHoist, NF = MEpiWgradAdam::kFlight;
+  MEpiWgradAdam epi{pr.dw, pr.K, pr.accumulate & 1, pr.db, (pr.accumulate >> 1) & 1, fused ? T : nullptr, c0, r0,
+                    (gbl_f32x4*)tg.param, (gbl_f32x4*)tg.exp_avg, (gbl_f32x4*)tg.exp_avg_sq, {}, {}, {}};
   GemmArgs g{(const bf16*)pr.x, pr.ldx, (const bf16*)pr.dy, pr.lddy, pr.K, pr.N, pr.M, 0, 0};
+  OVQA_APROBE(0);
+  // the two device scalars of the step, fetched in front of the K loop (behind the state loads they would be waited for
+  // together with all of them: the vector-memory counter is in order)
+  uint32_t step_t = 1u;
+  float lr_scale = 1.f;
+  if (fused) {
+    if (kc.step_ptr) step_t = *kc.step_ptr;
+    if (kc.lr_scale_ptr) lr_scale = *kc.lr_scale_ptr;
+  }
+  if (pr.M < BK) epi.last_k_step();  // (no K step at all: the gradient is zero, the update is still applied)
   gemm_tile_glds<true, true, MEpiWgradAdam, true, 2, 8, 128, 128>(g, c0, r0, epi, smem);
   if (!fused) return;
-  __syncthreads();  // the tile is complete
-  const AdamK ak = adam_consts(kc.lr, kc.lr_scale_ptr, kc.beta1, kc.beta2, kc.eps, kc.weight_decay, kc.grad_scale, kc.step_ptr);
-  const int tid = threadIdx.x, q = tid & 31;
-#pragma unroll 2
-  for (int pass = 0; pass < 8; pass++) {
-    const int ln = pass * 16 + (tid >> 5);
-    float* slot = T + ln * 128 + (((q ^ ln) & 31) << 2);
-    const f32x4 g4 = *reinterpret_cast<const f32x4*>(slot);
-    const int64_t e4 = ((int64_t)(c0 + ln) * pr.K + r0 + q * 4) >> 2;  // (K % 128 == 0: 16-byte aligned)
-    f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(tg.param) + e4);
-    f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(tg.exp_avg) + e4);
-    f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(tg.exp_avg_sq) + e4);
+  // the accumulators are in LDS: their registers take the state of the remaining passes, all of it in flight before the
+  // barrier (the addresses depend on the tile table entry alone)
+  f32x4 pp[NP], mm[NP], vv[NP];
+#pragma unroll
+  for (int pass = 0; pass < NH; pass++) {
+    pp[pass] = epi.hp[pass]; mm[pass] = epi.hm[pass]; vv[pass] = epi.hv[pass];
+  }
+#pragma unroll
+  for (int pass = NH; pass < NF; pass++) epi.load_pass(pass, pp[pass], mm[pass], vv[pass]);
+  __builtin_amdgcn_sched_barrier(0);  // (loads first, updates and stores behind them in issue order)
+  OVQA_APROBE(2);
+  const AdamK ak = adam_consts(kc.lr, &lr_scale, kc.beta1, kc.beta2, kc.eps, kc.weight_decay, kc.grad_scale, &step_t);
+  lds_barrier();  // the tile is complete
+  const int tid = threadIdx.x;
+  // One wait for everything issued so far, written out: the compiler would put the same vmcnt(0) in front of the first
+  // update (the K loop's direct-to-LDS loads count as flat accesses, after which it trusts no count), but it would go on
+  // doing so -- the last pass would wait for every store of the passes before it.  A wait it can see resets its count.
+  __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
+#pragma unroll
+  for (int pass = 0; pass < NP; pass++) {
+    float* slot = T + adam_tile_chunk(adam_row_of(pass, tid), (tid & 31) * 4);
+    f32x4 g4 = lds_read16_nowait(lds_offset(reinterpret_cast<const char*>(slot)));
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(g4)::"memory");
+    const int64_t t4 = epi.tile_piece();
+    const uint32_t off = epi.piece_off(pass);
     bf16x4 s4;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      float pk = pp[k], mk = mm[k], vk = vv[k];
+      float pk = pp[pass][k], mk = mm[pass][k], vk = vv[pass][k];
       adam_update1(ak, g4[k], pk, mk, vk);
-      pp[k] = pk; mm[k] = mk; vv[k] = vk;
+      pp[pass][k] = pk; mm[pass][k] = mk; vv[pass][k] = vk;
       s4[k] = (bf16)pk;
     }
-    __builtin_nontemporal_store(pp, reinterpret_cast<f32x4*>(tg.param) + e4);
-    __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(tg.exp_avg) + e4);
-    __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(tg.exp_avg_sq) + e4);
-    reinterpret_cast<bf16x4*>(tg.shadow)[e4] = s4;
+    __builtin_nontemporal_store(pp[pass], epi.at(epi.param + t4, off));
+    __builtin_nontemporal_store(mm[pass], epi.at(epi.exp_avg + t4, off));
+    __builtin_nontemporal_store(vv[pass], epi.at(epi.exp_avg_sq + t4, off));
+    *epi.at((gbl_bf16x4*)tg.shadow + t4, off >> 1) = s4;
     *reinterpret_cast<bf16x4*>(slot) = s4;  // (this thread's own 16-byte slot: its first 8 bytes now hold the bf16 values)
+    if (pass + NF < NP) epi.load_pass(pass + NF, pp[pass + NF], mm[pass + NF], vv[pass + NF]);  // (into the registers just freed)
   }
-  __syncthreads();
-  bf16* tt = reinterpret_cast<bf16*>(tg.transposed);
+  OVQA_APROBE(3);
+  lds_barrier();  // every row's bf16 values are in LDS (the state stores stay in flight)
+  __attribute__((address_space(1))) bf16* tt = (__attribute__((address_space(1))) bf16*)tg.transposed;
 #pragma unroll
   for (int pass = 0; pass < 4; pass++) {
-    const int li = pass * 32 + (tid >> 4);  // input feature = row of the transposed tile
-    const int cn = (tid & 15) * 8;          // 8 consecutive output features
-    bf16x8 o;
+    const int li = adam_gather_li(pass, tid);  // input feature = row of the transposed tile
+    const int cn = adam_gather_ln0(tid);       // 8 consecutive output features
+    uint32_t h[8];
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const int ln = cn + e;
-      o[e] = reinterpret_cast<const bf16*>(T + ln * 128 + ((((li >> 2) ^ ln) & 31) << 2))[li & 3];
-    }
-    *reinterpret_cast<bf16x8*>(tt + (int64_t)(r0 + li) * tg.ld_transposed + c0 + cn) = o;
+    for (int e = 0; e < 8; e++)
+      h[e] = lds_read_u16_nowait(lds_offset(reinterpret_cast<const char*>(T + adam_tile_chunk(cn + e, li))) + 2 * (li & 3));
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(h[4]), "+v"(h[5]), "+v"(h[6]), "+v"(h[7])::"memory");
+    *(gbl_u32x4*)(tt + (int64_t)(r0 + li) * tg.ld_transposed + c0 + cn) =
+        u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
   }
+  OVQA_APROBE(4);
+#ifdef OVQA_PHASE_PROBE
+  if (threadIdx.x == 0 && blockIdx.x < 4096)
+    g_probe_adam[blockIdx.x][5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                                  ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+#endif
 }
 
 // (Rounds 4-5 carried a 256 x 256-tile form of the grouped dW here -- one 16-wave workgroup per CU, ring of four 32-deep half
