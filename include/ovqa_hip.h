@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define OVQA_ABI_VERSION 11
+#define OVQA_ABI_VERSION 12
 
 typedef enum {
   OVQA_OK = 0,
@@ -330,6 +330,33 @@ int ovqa_attention_fwd_prefix_lm(int dtype, const void* q, int64_t ldq, const vo
                                  int64_t ldv, const float* key_mask, int64_t msb, int64_t msh, int64_t causal_tail,
                                  void* o, int64_t ldo, float* lse, int64_t B, int64_t H, int64_t n, int64_t d,
                                  float scale, void* stream);
+/* The prefix-LM form as a TRAINABLE operation (ABI 12): what ovqa_attention_fwd_prefix_lm computes, with what a backward
+ * pass needs -- the log-sum-exp (required), the rounding residual o_lo (optional, as ovqa_attention_fwd) and dropout on the
+ * probabilities (att_drop, element index ((b*H+h)*n+i)*n+j as everywhere; NULL / p == 0: off).
+ *   replaces: the same mask of MMT.forward (mmf_m4c.py:310-340) as BertSelfAttention sees it in TRAINING, where the dense
+ *             (B, 1, n, n) tensor forces the per-query-mask kernel forms that read n x n mask values per (b, h) from HBM.
+ *   The call computes the expression of ovqa_attention_fwd on the dense mask ((s scale + m - lse) log2e; a masked
+ *   probability is exactly 0 either way): wherever every query sees a key whose mask value is 0, o, o_lo and lse are
+ *   bit-identical to that call with -inf above the corner's diagonal.
+ *   bf16 only, d in {64, 96, 128} with 16-byte aligned rows, any length, 0 <= causal_tail <= n; no probabilities returned.
+ *   ovqa_last_dispatch() = "mfma" / "mfma-stream".  Other shapes, and OVQA_FORCE_SIMPLE=1 (there is no VALU form):
+ *   OVQA_ERR_UNSUPPORTED -- the caller passes the dense mask to ovqa_attention_fwd instead. */
+int ovqa_attention_fwd_prefix_lm_train(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                       int64_t ldv, const float* key_mask, int64_t msb, int64_t msh, int64_t causal_tail,
+                                       void* o, int64_t ldo, float* lse, void* o_lo, int64_t B, int64_t H, int64_t n,
+                                       int64_t d, float scale, const ovqa_dropout* att_drop, void* stream);
+/* Its backward (ABI 12): dq, dk, dv of ovqa_attention_bwd for the mask of mmf_m4c.py:310-340 given as key row +
+ * causal_tail; o, o_lo, lse and att_drop as the forward call wrote / took them, delta fp32 [B,H,n] scratch.  In the masked
+ * corner P is exactly 0, so dS and the dV contribution there are exactly 0, with dropout on or off: bit-identical to
+ * ovqa_attention_bwd on the dense mask under the condition above.  Always the two-kernel LDS-resident backward (n <= 256
+ * for d = 64 / 192 otherwise) or the streaming backward; no d_att / d_lse.  Same shapes, dispatch strings and
+ * OVQA_ERR_UNSUPPORTED cases as the forward. */
+int ovqa_attention_bwd_prefix_lm(int dtype, const void* d_o, int64_t lddo, const void* q, int64_t ldq, const void* k,
+                                 int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo, const void* o_lo,
+                                 const float* lse, const float* key_mask, int64_t msb, int64_t msh, int64_t causal_tail,
+                                 void* dq, int64_t lddq, void* dk_, int64_t lddk, void* dv_, int64_t lddv, float* delta,
+                                 int64_t B, int64_t H, int64_t n, int64_t d, float scale, const ovqa_dropout* att_drop,
+                                 void* stream);
 
 /* Self-attention forward with the Q/K/V projections inside: MultiHeadAttention.forward with queries is keys is
  * values (attentions.py:316-326 -> :49-57; the MCAN SA blocks, encoders.py:46-49, and the M4C MMT layers):

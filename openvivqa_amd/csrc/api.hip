@@ -459,6 +459,61 @@ int ovqa_attention_fwd_prefix_lm(int dtype, const void* q, int64_t ldq, const vo
   return attention_fwd_mfma(form, a, as_stream(stream));
 }
 
+int ovqa_attention_fwd_prefix_lm_train(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
+                                       int64_t ldv, const float* key_mask, int64_t msb, int64_t msh, int64_t causal_tail,
+                                       void* o, int64_t ldo, float* lse, void* o_lo, int64_t B, int64_t H, int64_t n,
+                                       int64_t d, float scale, const ovqa_dropout* att_drop, void* stream) {
+  OVQA_REQUIRE(dtype == OVQA_BF16, OVQA_ERR_UNSUPPORTED, "attention_fwd_prefix_lm_train: bf16 only");
+  OVQA_REQUIRE(B >= 0 && H > 0 && n >= 0 && d > 0 && causal_tail >= 0 && causal_tail <= n, OVQA_ERR_BAD_ARG,
+               "attention_fwd_prefix_lm_train: bad sizes");
+  if (B == 0 || n == 0) return OVQA_OK;
+  OVQA_REQUIRE(q && k && v && o && lse, OVQA_ERR_BAD_ARG, "attention_fwd_prefix_lm_train: null pointer");
+  OVQA_REQUIRE(ldq >= H * d && ldk >= H * d && ldv >= H * d && ldo >= H * d, OVQA_ERR_BAD_ARG,
+               "attention_fwd_prefix_lm_train: row stride smaller than H*d");
+  OVQA_REQUIRE(B * H <= 0x7fffffff, OVQA_ERR_UNSUPPORTED, "attention_fwd_prefix_lm_train: B*H too large");
+  OVQA_REQUIRE(B * H * n * n < (1ll << 32) || !att_drop || att_drop->p <= 0.f, OVQA_ERR_UNSUPPORTED,
+               "attention_fwd_prefix_lm_train: dropout on more than 2^32 probabilities");
+  ovqa::AttnArgs a{q, k, v, ldq, ldk, ldv, key_mask, msb, msh, 0, o, ldo, lse, nullptr,
+                   (int)B, (int)H, (int)n, (int)n, (int)d, (int)d, scale, make_drop_args(att_drop)};
+  a.o_lo = o_lo;
+  a.tail = (int)causal_tail;
+  const int form = attention_fwd_form(a);
+  OVQA_REQUIRE(form != ATT_NONE, OVQA_ERR_UNSUPPORTED,
+               "attention_fwd_prefix_lm_train: shape not covered by the MFMA forward kernels (d in {64, 96, 128}, 16-byte "
+               "aligned rows): pass the dense (B, 1, n, n) mask to ovqa_attention_fwd instead");
+  return attention_fwd_mfma(form, a, as_stream(stream));
+}
+
+int ovqa_attention_bwd_prefix_lm(int dtype, const void* d_o, int64_t lddo, const void* q, int64_t ldq, const void* k,
+                                 int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo, const void* o_lo,
+                                 const float* lse, const float* key_mask, int64_t msb, int64_t msh, int64_t causal_tail,
+                                 void* dq, int64_t lddq, void* dk_, int64_t lddk, void* dv_, int64_t lddv, float* delta,
+                                 int64_t B, int64_t H, int64_t n, int64_t d, float scale, const ovqa_dropout* att_drop,
+                                 void* stream) {
+  OVQA_REQUIRE(dtype == OVQA_BF16, OVQA_ERR_UNSUPPORTED, "attention_bwd_prefix_lm: bf16 only");
+  OVQA_REQUIRE(B >= 0 && H > 0 && n >= 0 && d > 0 && causal_tail >= 0 && causal_tail <= n, OVQA_ERR_BAD_ARG,
+               "attention_bwd_prefix_lm: bad sizes");
+  if (B == 0 || n == 0) return OVQA_OK;
+  OVQA_REQUIRE(d_o && q && k && v && o && lse && dq && dk_ && dv_ && delta, OVQA_ERR_BAD_ARG,
+               "attention_bwd_prefix_lm: null pointer");
+  OVQA_REQUIRE(lddo >= H * d && ldq >= H * d && ldk >= H * d && ldv >= H * d && ldo >= H * d && lddq >= H * d &&
+                   lddk >= H * d && lddv >= H * d, OVQA_ERR_BAD_ARG, "attention_bwd_prefix_lm: row stride smaller than H*d");
+  OVQA_REQUIRE(B * H <= 0x7fffffff, OVQA_ERR_UNSUPPORTED, "attention_bwd_prefix_lm: B*H too large");
+  OVQA_REQUIRE(B * H * n * n < (1ll << 32) || !att_drop || att_drop->p <= 0.f, OVQA_ERR_UNSUPPORTED,
+               "attention_bwd_prefix_lm: dropout on more than 2^32 probabilities");
+  ovqa::AttnBwdArgs a{d_o, q, k, v, o, nullptr, lddo, ldq, ldk, ldv, ldo, lse, key_mask, msb, msh, 0, dq, dk_, dv_,
+                      lddq, lddk, lddv, delta, (int)B, (int)H, (int)n, (int)n, (int)d, (int)d, scale,
+                      make_drop_args(att_drop), nullptr};
+  a.o_lo = o_lo;
+  a.tail = (int)causal_tail;
+  const int form = attention_bwd_form(a);
+  OVQA_REQUIRE(form != ATT_NONE, OVQA_ERR_UNSUPPORTED,
+               "attention_bwd_prefix_lm: shape not covered by the MFMA backward kernels (d in {64, 96, 128}, 16-byte aligned "
+               "rows): pass the dense (B, 1, n, n) mask to ovqa_attention_bwd instead");
+  g_dispatch = form == ATT_RESIDENT ? "mfma" : "mfma-stream";
+  return form == ATT_RESIDENT ? ovqa::mfma_attention_bwd(a, as_stream(stream)) : ovqa::stream_attention_bwd(a, as_stream(stream));
+}
+
 int ovqa_attention_qkv_fwd(int dtype, const void* x, int64_t ldx, const void* w, const float* bias, void* qkv,
                            int64_t ldqkv, const float* mask, int64_t msb, int64_t msh, void* o, int64_t ldo, float* lse,
                            void* o_lo, int64_t B, int64_t H, int64_t n, int64_t d_model, int64_t d, float scale,

@@ -676,6 +676,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
   const float lse = a.lse[((int64_t)b * a.H + h) * nq + qc];
   if (qok && lane < 32) a.delta[((int64_t)b * a.H + h) * nq + q] = delta;
   const float* mrow = a.mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh + (int64_t)qc * a.msq : nullptr;
+  // prefix-LM corner (a.tail, key-row masks only; see attn_fwd_core): this lane's query sees no key > qlim.  P is exactly 0
+  // there, as exp2 of the dense mask's -inf is, so dS is what the per-query-mask form computes, bit for bit.
+  const int qlim = (row_mask && a.tail && q >= nq - a.tail) ? q : 0x7fffffff;
   DropState dst{};
   uint32_t rbase = 0;
   if constexpr (DROP) {
@@ -716,7 +719,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
           const int r = 4 * g4 + e, key = key0 + e;
           float p;
           if (row_mask) {
-            p = exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);
+            p = key > qlim ? 0.f : exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);
           } else {
             p = 0.f;
             if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
@@ -730,7 +733,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
         const int key = t * 32 + acc_row(r, lane);
         float p;
         if (row_mask) {
-          p = exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);  // -inf beyond nk -> 0
+          p = key > qlim ? 0.f : exp2_fast((st[r] * a.scale + mlds[key] - lse) * LOG2E);  // -inf beyond nk -> 0
         } else {
           p = 0.f;
           if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
@@ -816,6 +819,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArg
   const float* mcol = a.mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh + (kok ? key : 0) : nullptr;
   constexpr bool row_mask = ROWMASK;  // key-padding mask: one value per key column, i.e. per lane
   const float mconst = (row_mask && mcol) ? mcol[0] : 0.f;
+  // prefix-LM corner (a.tail, key-row masks only): this lane's key is hidden from the queries qlo <= qi < key, the
+  // decoding positions in front of it.  tail = 0: qlo = nq, no query.
+  const int qlo = row_mask ? nq - a.tail : nq;
   DropState dst{};
   uint32_t pbase = 0;  // ((b*H+h)*nq) * nk + key: element (qi, key) is pbase + qi * nk
   if constexpr (DROP) {
@@ -849,7 +855,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArg
     for (int r = 0; r < 16; r++) {
       const int qi = t * 32 + acc_row(r, lane);
       float pv = 0.f;
-      if (qi < nq && kok) {
+      if (qi < nq && kok && !(row_mask && qi >= qlo && qi < key)) {
         const float mv = row_mask ? mconst : (mcol ? mcol[(int64_t)qi * a.msq] : 0.f);
         pv = exp2_fast((s_[r] * a.scale + mv - ls[qi]) * LOG2E);
       }
@@ -2066,6 +2072,7 @@ int launch_bwd(const ovqa::AttnBwdArgs& a, hipStream_t st) {
   if (a.dk == 96) return launch_bwd_two<96>(a, st);
   if (a.dk == 128) return launch_bwd_two<128>(a, st);
   if (a.drop.p > 0.f) return launch_bwd_two<64>(a, st);  // the role-split / merged forms have no dropout
+  if (a.tail > 0) return launch_bwd_two<64>(a, st);      // ... and no prefix-LM corner
   const int64_t nprob = (int64_t)a.B * a.H;
   const bool rowmask = a.msq == 0;
   if (a.nk > 32 && a.nk <= 128 && a.nq <= 128) {  // one launch, role-split waves

@@ -346,6 +346,8 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dq_kernel(ovqa::AttnBwdAr
     lse = a.lse[((int64_t)b * a.H + h) * nq + qc];
     if (qok && lane < 32) a.delta[((int64_t)b * a.H + h) * nq + q] = delta;
   }
+  // prefix-LM corner (a.tail, key-row masks only): this lane's query sees no key > qlim (as attn_bwd_dq_mfma_kernel)
+  const int qlim = (ROWMASK && a.tail && q >= nq - a.tail) ? q : 0x7fffffff;
   DropState dst{};
   uint32_t rbase = 0;
   if constexpr (DROP) {
@@ -390,7 +392,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dq_kernel(ovqa::AttnBwdAr
           const int r = 4 * g4 + e, key = key0 + e;
           float p;
           if constexpr (ROWMASK) {
-            p = exp2_fast((st[r] * a.scale + ml[i0 + e] - lse) * LOG2E);  // -inf beyond n_k -> 0
+            p = key > qlim ? 0.f : exp2_fast((st[r] * a.scale + ml[i0 + e] - lse) * LOG2E);  // -inf beyond n_k -> 0
           } else {
             p = 0.f;
             if (key < nk) p = exp2_fast((st[r] * a.scale + (mrow ? mrow[key] : 0.f) - lse) * LOG2E);
@@ -429,8 +431,13 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dq_kernel(ovqa::AttnBwdAr
 //   dV^T += dO^T P~,  dK^T += Q^T dS  (dO^T / Q^T through transposing reads).
 // DROP: a lane walks a key column, its 4 consecutive accumulator rows are queries n_k elements apart: each element hashes
 // its own pair (as attn_bwd_dkv_mfma_kernel).
-template <int D, bool ROWMASK, bool DROP>
-__global__ __launch_bounds__(256) void attn_stream_bwd_dkv_kernel(ovqa::AttnBwdArgs a) {
+// TAIL (key-row masks only; the prefix-LM corner of a.tail): queries nq - tail <= qi < key do not see this lane's key, P is
+// exactly 0 there (as exp2 of a dense mask's -inf), so nothing reaches dV or dS.  A compile-time form of its own,
+// attn_stream_bwd_dkv_tail_kernel: as a run-time field the test cost attn_stream_bwd_dkv_kernel<128, true, *> 80 / 60 bytes
+// of scratch per lane, and the calls without a tail keep the code they had.
+template <int D, bool ROWMASK, bool DROP, bool TAIL>
+__device__ __forceinline__ void stream_bwd_dkv_body(const ovqa::AttnBwdArgs& a) {
+  static_assert(ROWMASK || !TAIL, "the prefix-LM corner goes with a key-row mask");
   constexpr int KS = Img<D>::KS, DT = Img<D>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -443,6 +450,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dkv_kernel(ovqa::AttnBwdA
   const int kc = kok ? key : nk - 1;
   const float* mcol = a.mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh + kc : nullptr;
   const float mconst = (ROWMASK && mcol) ? mcol[0] : 0.f;
+  const int qlo = TAIL ? nq - a.tail : nq;
   const int64_t prob = (int64_t)b * a.H + h;
   const bf16* qg = (const bf16*)a.q + (int64_t)b * nq * a.ldq + h * D;
   const bf16* gg = (const bf16*)a.d_o + (int64_t)b * nq * a.lddo + h * D;
@@ -493,7 +501,8 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dkv_kernel(ovqa::AttnBwdA
         const int li = sub * 32 + acc_row(r, lane), qi = t * KT + li;
         float mv = mconst;
         if constexpr (!ROWMASK) mv = (mcol && qi < nq) ? mcol[(int64_t)qi * a.msq] : 0.f;
-        const float pv = exp2_fast((s_[r] * a.scale + mv - ls[li]) * LOG2E);
+        float pv = exp2_fast((s_[r] * a.scale + mv - ls[li]) * LOG2E);
+        if constexpr (TAIL) pv = (qi >= qlo && qi < key) ? 0.f : pv;
         if constexpr (DROP) {
           const float mk = (qi < nq && kok && drop_keep(dst, pbase + (uint32_t)qi * (uint32_t)nk)) ? dst.inv_keep : 0.f;
           p[r] = pv * mk;
@@ -536,6 +545,15 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dkv_kernel(ovqa::AttnBwdA
   }
 }
 
+template <int D, bool ROWMASK, bool DROP>
+__global__ __launch_bounds__(256) void attn_stream_bwd_dkv_kernel(ovqa::AttnBwdArgs a) {
+  stream_bwd_dkv_body<D, ROWMASK, DROP, false>(a);
+}
+template <int D, bool DROP>
+__global__ __launch_bounds__(256) void attn_stream_bwd_dkv_tail_kernel(ovqa::AttnBwdArgs a) {
+  stream_bwd_dkv_body<D, true, DROP, true>(a);
+}
+
 // ------------------------------------------------------------------------------------------ launchers
 template <int D, bool ROWMASK, bool DROP>
 int launch_stream_fwd_t(const ovqa::AttnArgs& a, hipStream_t st) {
@@ -564,10 +582,18 @@ int launch_stream_bwd_t(const ovqa::AttnBwdArgs& a, hipStream_t st) {
                     lds, st, a);
   rc = ovqa_check_launch("attention_bwd(mfma-stream,dq)");
   if (rc != OVQA_OK) return rc;
+  const dim3 kgrid(nprob, (unsigned)((a.nk + QB - 1) / QB));
+  if constexpr (ROWMASK) {
+    if (a.tail > 0) {  // prefix-LM corner
+      rc = ensure_lds(attn_stream_bwd_dkv_tail_kernel<D, DROP>, lds, "attention_bwd(mfma-stream,dkv)");
+      if (rc != OVQA_OK) return rc;
+      OVQA_LAUNCH_TIMED((attn_stream_bwd_dkv_tail_kernel<D, DROP>), kgrid, dim3(256), lds, st, a);
+      return ovqa_check_launch("attention_bwd(mfma-stream,dkv)");
+    }
+  }
   rc = ensure_lds(attn_stream_bwd_dkv_kernel<D, ROWMASK, DROP>, lds, "attention_bwd(mfma-stream,dkv)");
   if (rc != OVQA_OK) return rc;
-  OVQA_LAUNCH_TIMED((attn_stream_bwd_dkv_kernel<D, ROWMASK, DROP>), dim3(nprob, (unsigned)((a.nk + QB - 1) / QB)), dim3(256),
-                    lds, st, a);
+  OVQA_LAUNCH_TIMED((attn_stream_bwd_dkv_kernel<D, ROWMASK, DROP>), kgrid, dim3(256), lds, st, a);
   return ovqa_check_launch("attention_bwd(mfma-stream,dkv)");
 }
 

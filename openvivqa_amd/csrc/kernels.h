@@ -59,6 +59,7 @@ struct AttnBwdArgs {
   // attention (a freshly initialised stack) dQ / dK are 100-3000x smaller than the terms that cancel; with
   // O = o + o_lo (16 significant bits) the error of delta drops by 2^8 (tests/test_kernels_gpu.py).
   const void* o_lo = nullptr;
+  int tail = 0;  // prefix-LM form, as AttnArgs::tail: key-mask rows (msq == 0) with nq == nk only; the two-kernel and streaming forms
 };
 // ---- attention_decode.hip: one query per row against an in-place K/V cache --------------
 struct AttnDecodeArgs {

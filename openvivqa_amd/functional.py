@@ -343,6 +343,14 @@ def _project_qkv(st, queries, keys, values):
     return q, k, v, "general", (q, k, v)
 
 
+def prefix_lm_train_enabled() -> bool:
+    """OVQA_PREFIX_LM_TRAIN=1: attention calls WITH a backward (or with dropout on the probabilities) whose mask carries the
+    ``_ovqa_prefix_lm`` hint (utils.prefix_lm_mask) run ovqa_attention_fwd_prefix_lm_train / ovqa_attention_bwd_prefix_lm.
+    Opt-in: same bits as the dense mask, fewer mask reads.  OVQA_NO_PREFIX_LM=1, OVQA_FORCE_SIMPLE=1
+    and fp32 keep the dense mask whatever this says (ops.attention_fwd_prefix_lm_ok)."""
+    return os.environ.get("OVQA_PREFIX_LM_TRAIN", "0") == "1"
+
+
 def _project_and_attend(st, queries, keys, values, mask, save_lse=True, lo_out=None):
     """Projections + attention core of a MultiHeadAttention call -> (o, lse, mode, saved projection buffers).
     Self-attention with a key mask (or none) and no probability dropout goes through ``ovqa_attention_qkv_fwd``:
@@ -378,11 +386,18 @@ def _project_and_attend(st, queries, keys, values, mask, save_lse=True, lo_out=N
         return o, lse, "cross", (q, kv)
     q, k, v, mode, bufs = _project_qkv(st, queries, keys, values)
     # a dense (B, 1, n, n) mask that its builder has described as "key mask row + causal corner of the last T positions"
-    # (modules/mmt.py, inference): the kernel computes the corner and reads the row out of LDS instead of n x n mask values
+    # (utils.prefix_lm_mask): the kernel computes the corner and reads the row out of LDS instead of n x n mask values
     hint = getattr(mask, "_ovqa_prefix_lm", None)
-    if (hint is not None and not save_lse and lo_out is None and st.get("att_drop") is None and st.get("same") == "all"
-            and not torch.is_grad_enabled() and ops.attention_fwd_prefix_lm_ok(q, a.h)):
-        return ops.attention_fwd_prefix_lm(q, k, v, hint[0], hint[1], a.h), None, mode, bufs
+    if hint is not None and st.get("same") == "all" and ops.attention_fwd_prefix_lm_ok(q, a.h):
+        if not save_lse and lo_out is None and st.get("att_drop") is None and not torch.is_grad_enabled():
+            return ops.attention_fwd_prefix_lm(q, k, v, hint[0], hint[1], a.h), None, mode, bufs
+        if prefix_lm_train_enabled():
+            # a backward to come (or dropout on the probabilities): the trainable form.  The block remembers the route
+            # (st is this call's own copy) and its backward hands ovqa_attention_bwd_prefix_lm the same row and tail.
+            st["prefix_lm"] = hint
+            o, lse = ops.attention_fwd_prefix_lm_train(q, k, v, hint[0], hint[1], a.h, att_drop=st.get("att_drop"),
+                                                       lo_out=lo_out)
+            return o, (lse if save_lse else None), mode, bufs
     o, lse, _ = ops.attention_fwd(q, k, v, mask, a.h, save_lse=save_lse, att_drop=st.get("att_drop"), lo_out=lo_out)
     return o, lse, mode, bufs
 
@@ -422,7 +437,9 @@ class _MHABlock(Function):
         # guided attention and the 20 x 20 question self-attention: the fc_o dX product runs inside the attention backward
         # kernel (ovqa_attention_bwd_do), dO never travels through HBM
         fuse_do = False
-        if mode in ("pre", "self") and st.get("att_drop") is None and os.environ.get("OVQA_NO_FUSED_DO", "0") != "1":
+        plm = st.get("prefix_lm")  # the forward took the prefix-LM route: (key row, tail); never the _bwd_do fusion
+        if (plm is None and mode in ("pre", "self") and st.get("att_drop") is None
+                and os.environ.get("OVQA_NO_FUSED_DO", "0") != "1"):
             wt_o = arena.transposed([a.fc_o.weight])
             q_chk = bufs[0] if mode == "pre" else bufs[0][..., :nqk]
             fuse_do = ops.attention_bwd_do_ok(dpre_d, wt_o, q_chk, keys if mode == "pre" else q_chk, ctx.mask, a.h)
@@ -435,7 +452,11 @@ class _MHABlock(Function):
             (qkv,) = bufs
             q, k, v = qkv[..., :nqk], qkv[..., nqk:2 * nqk], qkv[..., 2 * nqk:]
             dqkv = torch.empty_like(qkv)
-            if fuse_do:
+            if plm is not None:
+                ops.attention_bwd_prefix_lm(d_o, q, k, v, o, lse, plm[0], plm[1], a.h, o_lo=o_lo,
+                                            att_drop=st.get("att_drop"), dq=dqkv[..., :nqk], dk=dqkv[..., nqk:2 * nqk],
+                                            dv=dqkv[..., 2 * nqk:])
+            elif fuse_do:
                 ops.attention_bwd_do(dpre_d, wt_o, q, k, v, o, lse, ctx.mask, a.h, o_lo=o_lo, dq=dqkv[..., :nqk],
                                      dk=dqkv[..., nqk:2 * nqk], dv=dqkv[..., 2 * nqk:])
             else:

@@ -22,7 +22,7 @@ from torch import nn
 
 from .. import functional as Fn
 from .. import runtime as rt
-from ..utils import generate_sequential_mask
+from ..utils import prefix_lm_mask
 
 
 class BertSelfAttention(nn.Module):
@@ -200,15 +200,11 @@ class MMT(nn.Module):
     @staticmethod
     def _extended_mask(txt_mask, obj_mask, ocr_mask, steps, dec_emb):
         dec_mask = torch.zeros(dec_emb.size(0), 1, 1, steps, dtype=torch.float32, device=dec_emb.device)
-        mask = torch.cat([txt_mask, obj_mask, ocr_mask, dec_mask], dim=-1).float()
-        S = mask.size(-1)
-        ext = mask.repeat(1, 1, S, 1)
-        ext[:, :, -steps:, -steps:] = generate_sequential_mask(steps, device=ext.device)
-        # what this tensor IS, for the attention kernel (inference): the key row + a causal corner of `steps` positions --
-        # ovqa_attention_fwd_prefix_lm then reads S mask values per (b, h) instead of S x S (functional._project_and_attend)
-        if mask.shape[1] == 1 and mask.shape[2] == 1:
-            ext._ovqa_prefix_lm = (mask, steps)
-        return ext
+        mask = torch.cat([txt_mask, obj_mask, ocr_mask, dec_mask], dim=-1)
+        # the dense tensor, which also says what it IS (the key row + a causal corner of `steps` positions): the attention
+        # kernels then read S mask values per (b, h) instead of S x S, at inference and in training
+        # (functional._project_and_attend)
+        return prefix_lm_mask(mask, steps)
 
 
 class M4CDecodingHead(nn.Module):

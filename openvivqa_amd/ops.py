@@ -724,6 +724,54 @@ def attention_fwd_prefix_lm(q, k, v, key_mask, causal_tail, H, scale=None):
     return o
 
 
+def attention_fwd_prefix_lm_train(q, k, v, key_mask, causal_tail, H, scale=None, att_drop=None, lo_out=None):
+    """``attention_fwd_prefix_lm`` as a trainable operation (``ovqa_attention_fwd_prefix_lm_train``): also the log-sum-exp,
+    the rounding residual of o (``lo_out``, as ``attention_fwd``) and dropout on the probabilities (``att_drop``).  q / k / v
+    may be row-strided views (slices of one packed projection).  Returns (o [B, n, H*d], lse [B, H, n]); the gate is
+    ``attention_fwd_prefix_lm_ok``."""
+    _dev(q)
+    lib = _lib.load()
+    B, n = q.shape[0], q.shape[1]
+    d = q.shape[2] // H
+    assert k.shape[1] == n and v.shape[1] == n and v.shape[2] == q.shape[2] == k.shape[2]
+    scale = (1.0 / math.sqrt(d)) if scale is None else scale
+    o = torch.empty(B, n, H * d, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, n, dtype=torch.float32, device=q.device)
+    key_mask, sb, sh, sq = _mask_strides(key_mask, B, H, n, n)
+    assert sq == 0, "a key mask: one row per (b, h)"
+    lo = _lo_buffer(lo_out, o)
+    _lib.check(lib.ovqa_attention_fwd_prefix_lm_train(_dt(q), _p(q), _rows(q)[0], _p(k), _rows(k)[0], _p(v), _rows(v)[0],
+                                                      _p(key_mask), sb, sh, int(causal_tail), _p(o), H * d, _p(lse),
+                                                      _p(lo), B, H, n, d, float(scale), _drop(att_drop), _stream()),
+               "attention_fwd_prefix_lm_train")
+    return o, lse
+
+
+def attention_bwd_prefix_lm(d_o, q, k, v, o, lse, key_mask, causal_tail, H, scale=None, dq=None, dk=None, dv=None,
+                            att_drop=None, o_lo=None):
+    """Backward of ``attention_fwd_prefix_lm_train`` (``ovqa_attention_bwd_prefix_lm``): the key-mask row and the tail
+    instead of the dense mask of ``attention_bwd``, the same (dq, dk, dv)."""
+    _dev(q)
+    lib = _lib.load()
+    B, n = q.shape[0], q.shape[1]
+    d = q.shape[2] // H
+    assert k.shape[1] == n and v.shape[1] == n and v.shape[2] == q.shape[2] == k.shape[2]
+    scale = (1.0 / math.sqrt(d)) if scale is None else scale
+    dq = dq if dq is not None else torch.empty(B, n, H * d, dtype=q.dtype, device=q.device)
+    dk = dk if dk is not None else torch.empty(B, n, H * d, dtype=q.dtype, device=q.device)
+    dv = dv if dv is not None else torch.empty(B, n, H * d, dtype=q.dtype, device=q.device)
+    delta = torch.empty(B, H, n, dtype=torch.float32, device=q.device)
+    key_mask, sb, sh, sq = _mask_strides(key_mask, B, H, n, n)
+    assert sq == 0, "a key mask: one row per (b, h)"
+    if o_lo is not None:
+        assert o_lo.dtype == o.dtype == torch.bfloat16 and o_lo.shape == o.shape and _rows(o_lo)[0] == _rows(o)[0]
+    _lib.check(lib.ovqa_attention_bwd_prefix_lm(
+        _dt(q), _p(d_o), _rows(d_o)[0], _p(q), _rows(q)[0], _p(k), _rows(k)[0], _p(v), _rows(v)[0], _p(o), _rows(o)[0],
+        _p(o_lo), _p(lse), _p(key_mask), sb, sh, int(causal_tail), _p(dq), _rows(dq)[0], _p(dk), _rows(dk)[0], _p(dv),
+        _rows(dv)[0], _p(delta), B, H, n, d, float(scale), _drop(att_drop), _stream()), "attention_bwd_prefix_lm")
+    return dq, dk, dv
+
+
 def attention_qkv_fwd(x, w, bias, mask, H, scale=None, save_lse=True, lo_out=None):
     """Self-attention forward with the packed projections inside (``ovqa_attention_qkv_fwd``): x [B,n,d_model],
     w [3*H*d, d_model] (fc_q | fc_k | fc_v rows), bias fp32 [3*H*d] -> (qkv [B,n,3*H*d], o [B,n,H*d], lse).

@@ -29,6 +29,28 @@ def generate_sequential_mask(seq_len: int, device=None) -> torch.Tensor:
     return (torch.triu(torch.ones(seq_len, seq_len, device=device), diagonal=1) * MASK_VALUE).unsqueeze(0).unsqueeze(0)
 
 
+def prefix_lm_mask(key_row: torch.Tensor, tail: int) -> torch.Tensor:
+    """The dense (B, 1, n, n) additive mask of a prefix-LM layout (M4C's multimodal transformer, mmf_m4c.py:310-340): the
+    key-padding row ``key_row`` (B, 1, 1, n) repeated over the n queries, with the corner of the last ``tail`` positions
+    SET to ``generate_sequential_mask(tail)`` -- among them query i does not see keys j > i.
+
+    The returned tensor also says what it is: its attribute ``_ovqa_prefix_lm = (key_row as fp32, tail)`` lets the attention
+    blocks hand the kernels the row and the tail instead of n x n mask values per sample (``ovqa_attention_fwd_prefix_lm``
+    at inference, ``ovqa_attention_fwd_prefix_lm_train`` / ``ovqa_attention_bwd_prefix_lm`` with gradients), with the same
+    results bit for bit.  The description is exact when the row is 0 over the last ``tail`` keys (M4C's decoding positions
+    are never padded): the corner is set, not added.  The hint is an attribute of THIS tensor object: anything that makes a
+    new tensor of it (``.to(dtype)``, ``.to(device)``, ``.clone()``, arithmetic) drops it, and the attention call then
+    silently takes the dense-mask kernels -- correct, only slower."""
+    mask = key_row.float()
+    n = mask.size(-1)
+    ext = mask.repeat(1, 1, n, 1)
+    if tail > 0:
+        ext[:, :, -tail:, -tail:] = generate_sequential_mask(tail, device=ext.device)
+    if mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1:
+        ext._ovqa_prefix_lm = (mask, tail)
+    return ext
+
+
 def generate_self_attention_masks(padding_masks: torch.Tensor, sequential_masks: torch.Tensor) -> torch.Tensor:
     """OR of the two masks -> (B,1,T,T).  models/utils.py:68-73."""
     return torch.logical_or(padding_masks != 0, sequential_masks != 0).long() * MASK_VALUE
