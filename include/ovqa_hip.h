@@ -694,6 +694,40 @@ int ovqa_embed_scatter(int dtype, const int64_t* tokens, const void* drows, int6
 int ovqa_decoder_inputs(const int64_t* tokens, const float* emb, const float* pos_table, int64_t pos_rows, float* out,
                         float* self_mask, int64_t B, int64_t T, int64_t D, int64_t padding_idx, void* stream);
 int ovqa_dropout_apply(int dtype, const void* x, void* y, int64_t n, const ovqa_dropout* drop, void* stream);
+
+/* BERT embeddings (additive to ABI 12).   replaces: transformers' BertEmbeddings.forward as TextBert.forward calls it,
+ *     self.embeddings(txt_inds), models/mmf_m4c.py:266-267 (three nn.Embedding lookups, two adds, LayerNorm, dropout) with
+ *     its autograd, and the question's padding mask of :137-141.
+ *   ovqa_bert_embeddings_fwd (one launch): tokens int64 [B, T]; fp32 tables word [vocab, ld_word], pos [pos_rows, ld_pos],
+ *     type0 = row 0 of the token-type table (no token_type_ids are passed upstream: the only row read); gamma / beta fp32 [D].
+ *     For row r = b*T + t:  x = word[clamp(tok, 0, vocab-1)] + type0 + pos[t],  y[r] = dropout(LN(x; eps)), the dropout call
+ *     site `drop` (NULL or p == 0: off) on the flat element index r*D + c, as ovqa_dropout_apply.
+ *     -> y [B*T, D] of `dtype`; y32 fp32 [B*T, D] or NULL (the same values unrounded: the fp32 residual stream of the bf16
+ *        mode, as ovqa_layernorm_fwd's y_f32); mean / rstd fp32 [B*T]; mask fp32 [B, T] or NULL =
+ *        (tok == mask_padding_idx) * -10e4, -0.0 where unmasked (generate_padding_mask; the VOCABULARY's padding index).
+ *     T <= pos_rows, D % 4 == 0 and 16-byte aligned rows are required (OVQA_ERR_BAD_ARG); D <= 1024 (OVQA_ERR_UNSUPPORTED).
+ *   ovqa_bert_embeddings_bwd (three launches: dx rows + partial sums, column reduce, ovqa_embed_scatter's kernel): dy [B*T, D]
+ *     of `dtype` = the gradient w.r.t. y; mean / rstd from the forward; x is recomputed from the tables.  dx fp32 [B*T, D]
+ *     receives the gradient w.r.t. x; ws: ws_floats >= ceil(B*T / 8) * 3 * D floats of workspace.  Each output is stored (=) or
+ *     added to (+=) as its acc_* flag says:
+ *       dword [dword_rows >= vocab, ld_dword]: per-token sums of dx; rows no token names and row table_padding_idx
+ *         (nn.Embedding's padding_idx, BertConfig.pad_token_id) are zeros;
+ *       dpos [dpos_rows >= T, ld_dpos]: row t < T = sum over b of dx[b, t]; rows >= T zeros;
+ *       dtype_tab [dtype_rows >= 1, ld_dtype]: row 0 = sum over all rows of dx; other rows zeros;
+ *       dgamma / dbeta fp32 [D].
+ *     Every sum runs in a fixed order with plain stores (no atomics): two runs give the same bits. */
+int ovqa_bert_embeddings_fwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab,
+                             const float* pos, int64_t ld_pos, int64_t pos_rows, const float* type0, const float* gamma,
+                             const float* beta, float eps, void* y, float* y32, float* mean, float* rstd, float* mask,
+                             int64_t mask_padding_idx, int64_t B, int64_t T, int64_t D, const ovqa_dropout* drop,
+                             void* stream);
+int ovqa_bert_embeddings_bwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab,
+                             const float* pos, int64_t ld_pos, int64_t pos_rows, const float* type0, const float* gamma,
+                             const float* mean, const float* rstd, const void* dy, float* dx, float* ws, int64_t ws_floats,
+                             float* dword, int64_t ld_dword, int64_t dword_rows, int64_t table_padding_idx, int acc_word,
+                             float* dpos, int64_t ld_dpos, int64_t dpos_rows, int acc_pos, float* dtype_tab, int64_t ld_dtype,
+                             int64_t dtype_rows, int acc_type, float* dgamma, int acc_gamma, float* dbeta, int acc_beta,
+                             int64_t B, int64_t T, int64_t D, const ovqa_dropout* drop, void* stream);
 int ovqa_pool_fwd(int feat_dtype, int dtype, const void* feat, const void* hpre, const float* w2, const float* b2, float* att,
                   void* pooled, float* pooled32, int64_t B, int64_t N, int64_t D, const ovqa_dropout* drop, void* stream);
 int ovqa_pool_bwd(int feat_dtype, int dtype, const void* feat, const void* hpre, const float* w2, const float* att,

@@ -155,6 +155,11 @@ SIGNATURES = {
     "ovqa_decoder_inputs": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp],
     "ovqa_embed_scatter": [c_int, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_int, c_vp],
     "ovqa_dropout_apply": [c_int, c_vp, c_vp, c_i64, _DP, c_vp],
+    "ovqa_bert_embeddings_fwd": [c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, _DP, c_vp],
+    "ovqa_bert_embeddings_bwd": [c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_i64, c_int,
+                                 c_vp, c_int, c_vp, c_int, c_i64, c_i64, c_i64, _DP, c_vp],
     "ovqa_pool_fwd": [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, _DP, c_vp],
     "ovqa_pool_bwd": [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, _DP, c_vp],
     "ovqa_log_softmax_fwd": [c_int, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp],

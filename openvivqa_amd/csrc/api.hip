@@ -924,6 +924,72 @@ int ovqa_embed_scatter(int dtype, const int64_t* tokens, const void* drows, int6
                              padding_idx, accumulate, as_stream(stream));
 }
 
+// the checks the two BERT-embeddings entries share: nothing is launched (and nothing written) unless all of them hold
+static int bert_embeddings_args(const char* who, int dtype, const int64_t* tokens, const float* word, int64_t ld_word,
+                                int64_t vocab, const float* pos, int64_t ld_pos, int64_t pos_rows, const float* type0,
+                                const float* gamma, int64_t B, int64_t T, int64_t D) {
+  OVQA_REQUIRE(dtype_ok(dtype), OVQA_ERR_BAD_ARG, "%s: bad dtype", who);
+  OVQA_REQUIRE(B >= 0 && T >= 0 && D >= 1 && vocab >= 1 && pos_rows >= 1 && pos_rows < 65535, OVQA_ERR_BAD_ARG,
+               "%s: bad size", who);
+  OVQA_REQUIRE(T <= pos_rows, OVQA_ERR_BAD_ARG, "%s: %lld tokens per sample, the position table has %lld rows", who,
+               (long long)T, (long long)pos_rows);
+  OVQA_REQUIRE(D % 4 == 0, OVQA_ERR_BAD_ARG, "%s: the hidden size (%lld) must be a multiple of 4", who, (long long)D);
+  OVQA_REQUIRE(D <= 1024, OVQA_ERR_UNSUPPORTED, "%s: hidden sizes above 1024 (%lld) are not supported", who, (long long)D);
+  OVQA_REQUIRE(B * T * D < (1ll << 32) && B * T < (1ll << 31), OVQA_ERR_BAD_ARG, "%s: too many elements", who);
+  OVQA_REQUIRE(tokens && word && pos && type0 && gamma, OVQA_ERR_BAD_ARG, "%s: null pointer", who);
+  OVQA_REQUIRE(ld_word >= D && ld_pos >= D && ld_word % 4 == 0 && ld_pos % 4 == 0 && (uintptr_t)word % 16 == 0 &&
+                   (uintptr_t)pos % 16 == 0 && (uintptr_t)type0 % 16 == 0 && (uintptr_t)gamma % 16 == 0,
+               OVQA_ERR_BAD_ARG, "%s: table rows and gamma must be 16-byte aligned", who);
+  return OVQA_OK;
+}
+
+int ovqa_bert_embeddings_fwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab,
+                             const float* pos, int64_t ld_pos, int64_t pos_rows, const float* type0, const float* gamma,
+                             const float* beta, float eps, void* y, float* y32, float* mean, float* rstd, float* mask,
+                             int64_t mask_padding_idx, int64_t B, int64_t T, int64_t D, const ovqa_dropout* drop,
+                             void* stream) {
+  const int rc = bert_embeddings_args("bert_embeddings_fwd", dtype, tokens, word, ld_word, vocab, pos, ld_pos, pos_rows, type0,
+                                      gamma, B, T, D);
+  if (rc != OVQA_OK) return rc;
+  OVQA_REQUIRE(beta && y && mean && rstd, OVQA_ERR_BAD_ARG, "bert_embeddings_fwd: null pointer");
+  OVQA_REQUIRE((uintptr_t)beta % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)y32 % 16 == 0, OVQA_ERR_BAD_ARG,
+               "bert_embeddings_fwd: beta, y and y32 must be 16-byte aligned");
+  OVQA_REQUIRE(drop == nullptr || (drop->p >= 0.f && drop->p < 1.f), OVQA_ERR_BAD_ARG, "bert_embeddings_fwd: bad dropout p");
+  if (B == 0 || T == 0) return OVQA_OK;
+  g_dispatch = "stream";
+  return ovqa::bert_embeddings_fwd(dtype, tokens, word, ld_word, vocab, pos, ld_pos, type0, gamma, beta, eps, y, y32, mean,
+                                   rstd, mask, mask_padding_idx, B, T, D, make_drop_args(drop), as_stream(stream));
+}
+
+int ovqa_bert_embeddings_bwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab,
+                             const float* pos, int64_t ld_pos, int64_t pos_rows, const float* type0, const float* gamma,
+                             const float* mean, const float* rstd, const void* dy, float* dx, float* ws, int64_t ws_floats,
+                             float* dword, int64_t ld_dword, int64_t dword_rows, int64_t table_padding_idx, int acc_word,
+                             float* dpos, int64_t ld_dpos, int64_t dpos_rows, int acc_pos, float* dtype_tab, int64_t ld_dtype,
+                             int64_t dtype_rows, int acc_type, float* dgamma, int acc_gamma, float* dbeta, int acc_beta,
+                             int64_t B, int64_t T, int64_t D, const ovqa_dropout* drop, void* stream) {
+  const int rc = bert_embeddings_args("bert_embeddings_bwd", dtype, tokens, word, ld_word, vocab, pos, ld_pos, pos_rows, type0,
+                                      gamma, B, T, D);
+  if (rc != OVQA_OK) return rc;
+  OVQA_REQUIRE(B >= 1 && T >= 1, OVQA_ERR_BAD_ARG, "bert_embeddings_bwd: empty batch");
+  OVQA_REQUIRE(mean && rstd && dy && dx && ws && dword && dpos && dtype_tab && dgamma && dbeta, OVQA_ERR_BAD_ARG,
+               "bert_embeddings_bwd: null pointer");
+  OVQA_REQUIRE((uintptr_t)dy % 16 == 0 && (uintptr_t)dx % 16 == 0, OVQA_ERR_BAD_ARG,
+               "bert_embeddings_bwd: dy and dx must be 16-byte aligned");
+  OVQA_REQUIRE(ws_floats >= ovqa::bert_embeddings_bwd_blocks(B * T) * 3 * D, OVQA_ERR_BAD_ARG,
+               "bert_embeddings_bwd: the workspace holds %lld floats, %lld needed", (long long)ws_floats,
+               (long long)(ovqa::bert_embeddings_bwd_blocks(B * T) * 3 * D));
+  OVQA_REQUIRE(dword_rows >= vocab && dword_rows < (1ll << 31) && ld_dword >= D && dpos_rows >= T && dpos_rows < 65535 &&
+                   ld_dpos >= D && dtype_rows >= 1 && ld_dtype >= D,
+               OVQA_ERR_BAD_ARG, "bert_embeddings_bwd: a gradient table is smaller than what it receives");
+  OVQA_REQUIRE(drop == nullptr || (drop->p >= 0.f && drop->p < 1.f), OVQA_ERR_BAD_ARG, "bert_embeddings_bwd: bad dropout p");
+  g_dispatch = "stream";
+  return ovqa::bert_embeddings_bwd(dtype, tokens, word, ld_word, vocab, pos, ld_pos, type0, gamma, mean, rstd, dy, dx, ws, dword,
+                                   ld_dword, dword_rows, table_padding_idx, acc_word, dpos, ld_dpos, dpos_rows, acc_pos,
+                                   dtype_tab, ld_dtype, dtype_rows, acc_type, dgamma, acc_gamma, dbeta, acc_beta, B, T, D,
+                                   make_drop_args(drop), as_stream(stream));
+}
+
 int ovqa_dropout_apply(int dtype, const void* x, void* y, int64_t n, const ovqa_dropout* drop, void* stream) {
   OVQA_REQUIRE(dtype_ok(dtype), OVQA_ERR_BAD_ARG, "dropout_apply: bad dtype");
   OVQA_REQUIRE(n >= 0 && n < (1ll << 32), OVQA_ERR_BAD_ARG, "dropout_apply: bad size");

@@ -173,6 +173,18 @@ int decoder_inputs(const int64_t* tokens, const float* emb, const float* pos_tab
 int embed_scatter(int dtype, const int64_t* tokens, const void* drows, int64_t ld_rows, float* dtable, int64_t ld_table,
                   int64_t rows_table, int64_t B, int64_t T, int64_t width, int time_major, int64_t padding_idx,
                   int accumulate, hipStream_t st);
+// BERT embeddings (gather of three table rows + LayerNorm + dropout; backward = dx kernel, reduce kernel, embed_scatter)
+int64_t bert_embeddings_bwd_blocks(int64_t R);  // partial rows of 3 * D floats the backward's workspace holds
+int bert_embeddings_fwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab, const float* pos,
+                        int64_t ld_pos, const float* type0, const float* gamma, const float* beta, float eps, void* y,
+                        float* y32, float* mean, float* rstd, float* mask, int64_t mask_padding_idx, int64_t B, int64_t T,
+                        int64_t D, const DropArgs& da, hipStream_t st);
+int bert_embeddings_bwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab, const float* pos,
+                        int64_t ld_pos, const float* type0, const float* gamma, const float* mean, const float* rstd,
+                        const void* dy, float* dx, float* ws, float* dword, int64_t ld_dword, int64_t dword_rows,
+                        int64_t table_padding_idx, int acc_word, float* dpos, int64_t ld_dpos, int64_t dpos_rows, int acc_pos,
+                        float* dtype_tab, int64_t ld_dtype, int64_t dtype_rows, int acc_type, float* dgamma, int acc_gamma,
+                        float* dbeta, int acc_beta, int64_t B, int64_t T, int64_t D, const DropArgs& da, hipStream_t st);
 int dropout_apply(int dtype, const void* x, void* y, int64_t n, const DropArgs& da, hipStream_t st);
 int pool_fwd(int feat_dtype, int dtype, const void* feat, const void* hpre, const float* w2, const float* b2, float* att,
              void* pooled, float* pooled32, int64_t B, int64_t N, int64_t D, const DropArgs& da, hipStream_t st);

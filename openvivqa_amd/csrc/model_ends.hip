@@ -139,6 +139,224 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const int64_t* __res
   }
 }
 
+// ---- BERT embeddings (transformers' BertEmbeddings as TextBert.forward calls it, models/mmf_m4c.py:266-267) ---------------
+//   x[r][:] = word[clamp(tok(r))][:] + type[0][:] + pos[t][:],  r = b * T + t        (no token_type_ids: row 0 for every token)
+//   y[r][:] = dropout(LN(x[r][:]))                                                 (eps 1e-12, hidden_dropout_prob)
+// -- three nn.Embedding gathers, two adds, a LayerNorm and a dropout of stock torch, and their seven autograd twins.  One wave
+// per row: D <= 1024 floats are BE_MAXJ float4 pieces per lane (3 at D = 768), so the row lives in registers over the two-pass
+// LayerNorm (mean, then the centred squares: the same arithmetic as layernorm.hip) and nothing but y is written.  The
+// backward does NOT get x from the forward: 3 KiB of table reads per row recompute it.
+constexpr int BE_MAXJ = 4;      // float4 pieces per lane: D <= 1024
+constexpr int BE_BWD_ROWS = 8;  // rows per workgroup of bert_embeddings_bwd_dx_kernel: two per wave, one partial row per workgroup
+
+__device__ __forceinline__ void be_load_x(const float* __restrict__ w, const float* __restrict__ ty,
+                                          const float* __restrict__ p, int D, int l, float (&x)[BE_MAXJ][4]) {
+#pragma unroll
+  for (int j = 0; j < BE_MAXJ; j++) {
+    const int c = (j * 64 + l) * 4;
+    if (c < D) {
+      const float4 a = *reinterpret_cast<const float4*>(w + c), b = *reinterpret_cast<const float4*>(ty + c),
+                   q = *reinterpret_cast<const float4*>(p + c);
+      x[j][0] = (a.x + b.x) + q.x; x[j][1] = (a.y + b.y) + q.y; x[j][2] = (a.z + b.z) + q.z; x[j][3] = (a.w + b.w) + q.w;
+    } else {
+      x[j][0] = x[j][1] = x[j][2] = x[j][3] = 0.f;
+    }
+  }
+}
+__device__ __forceinline__ void be_store4(float* p, const float (&v)[4]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void be_store4(bf16* p, const float (&v)[4]) {
+  bf16x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; e++) o[e] = (bf16)v[e];
+  *reinterpret_cast<bf16x4*>(p) = o;
+}
+__device__ __forceinline__ void be_load4(const float* p, float (&v)[4]) {
+  const float4 a = *reinterpret_cast<const float4*>(p);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+}
+__device__ __forceinline__ void be_load4(const bf16* p, float (&v)[4]) {
+  const bf16x4 a = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+  for (int e = 0; e < 4; e++) v[e] = (float)a[e];
+}
+__device__ __forceinline__ int64_t be_clamp(int64_t tok, int64_t vocab) {
+  return tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);  // (torch raises on an out-of-range index; never read outside)
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embeddings_fwd_kernel(
+    const int64_t* __restrict__ tokens, const float* __restrict__ word, int64_t ld_word, int64_t vocab,
+    const float* __restrict__ pos, int64_t ld_pos, const float* __restrict__ type0, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float eps, T* __restrict__ y, float* __restrict__ y32, float* __restrict__ mean,
+    float* __restrict__ rstd, float* __restrict__ mask, int64_t mask_padding_idx, int R, int Tn, int D, DropArgs da) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+  if (r >= R) return;
+  const int64_t tok = tokens[r];
+  // txt_mask of mmf_m4c.py:137-141 from the same pass: (tok == pad) * -10e4, -0.0 where unmasked (as embed_gather_kernel)
+  if (mask != nullptr && l == 0) mask[r] = tok == mask_padding_idx ? -100000.f : -0.f;
+  float x[BE_MAXJ][4];
+  be_load_x(word + be_clamp(tok, vocab) * ld_word, type0, pos + (int64_t)(r % Tn) * ld_pos, D, l, x);
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < BE_MAXJ; j++) s += (x[j][0] + x[j][1]) + (x[j][2] + x[j][3]);
+  const float mu = wave_sum(s) / (float)D;
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < BE_MAXJ; j++)
+    if ((j * 64 + l) * 4 < D) {
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const float d = x[j][e] - mu;
+        sq += d * d;
+      }
+    }
+  const float rs = rsqrtf(wave_sum(sq) / (float)D + eps);
+  if (l == 0) {
+    mean[r] = mu;
+    rstd[r] = rs;
+  }
+  const DropState ds = drop_init(da);
+#pragma unroll
+  for (int j = 0; j < BE_MAXJ; j++) {
+    const int c = (j * 64 + l) * 4;
+    if (c >= D) continue;
+    float g[4], b[4], v[4];
+    be_load4(gamma + c, g);
+    be_load4(beta + c, b);
+    const int64_t at = (int64_t)r * D + c;  // flat element index of the dropout call site, as ovqa_dropout_apply
+#pragma unroll
+    for (int e = 0; e < 4; e++) v[e] = fmaf((x[j][e] - mu) * rs, g[e], b[e]) * drop_mul(ds, (uint32_t)(at + e));
+    be_store4(y + at, v);
+    if (y32 != nullptr) be_store4(y32 + at, v);
+  }
+}
+
+// Backward, first kernel: dx[r][:] (fp32: the rows ovqa_embed_scatter sums into the word table and the reduce kernel sums
+// over b into the position table), with g = dy * keep / (1 - p), xh = (x - mean) rstd, dxh = g gamma:
+//   dx = rstd (dxh - mean_c(dxh) - xh mean_c(dxh xh))
+// and one partial row per workgroup, part[blockIdx.x][0 .. 3D) = [sum_r g xh | sum_r g | sum_r dx] over its BE_BWD_ROWS rows
+// (dgamma, dbeta and the token-type row): each wave adds its two rows in registers, the four waves add into LDS one after the
+// other -- a fixed order, no atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void bert_embeddings_bwd_dx_kernel(
+    const int64_t* __restrict__ tokens, const float* __restrict__ word, int64_t ld_word, int64_t vocab,
+    const float* __restrict__ pos, int64_t ld_pos, const float* __restrict__ type0, const float* __restrict__ gamma,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const T* __restrict__ dy, float* __restrict__ dx,
+    float* __restrict__ part, int R, int Tn, int D, DropArgs da) {
+  __shared__ float s_acc[3][BE_MAXJ * 256];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const DropState ds = drop_init(da);
+  float ag[BE_MAXJ][4], ab[BE_MAXJ][4], ax[BE_MAXJ][4], gm[BE_MAXJ][4];
+#pragma unroll
+  for (int j = 0; j < BE_MAXJ; j++) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) ag[j][e] = ab[j][e] = ax[j][e] = gm[j][e] = 0.f;
+    if ((j * 64 + l) * 4 < D) be_load4(gamma + (j * 64 + l) * 4, gm[j]);
+  }
+  constexpr int RPW = BE_BWD_ROWS / 4;
+  for (int i = 0; i < RPW; i++) {
+    const int r = blockIdx.x * BE_BWD_ROWS + w * RPW + i;
+    if (r >= R) break;  // (wave-uniform)
+    float x[BE_MAXJ][4], g[BE_MAXJ][4];
+    be_load_x(word + be_clamp(tokens[r], vocab) * ld_word, type0, pos + (int64_t)(r % Tn) * ld_pos, D, l, x);
+    const float mu = mean[r], rs = rstd[r];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < BE_MAXJ; j++) {
+      const int c = (j * 64 + l) * 4;
+      if (c < D) {
+        const int64_t at = (int64_t)r * D + c;
+        be_load4(dy + at, g[j]);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          g[j][e] *= drop_mul(ds, (uint32_t)(at + e));
+          x[j][e] = (x[j][e] - mu) * rs;  // xh
+          const float dxh = g[j][e] * gm[j][e];
+          s1 += dxh;
+          s2 = fmaf(dxh, x[j][e], s2);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++) g[j][e] = x[j][e] = 0.f;
+      }
+    }
+    s1 = wave_sum(s1) / (float)D;
+    s2 = wave_sum(s2) / (float)D;
+#pragma unroll
+    for (int j = 0; j < BE_MAXJ; j++) {
+      const int c = (j * 64 + l) * 4;
+      if (c >= D) continue;
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        o[e] = rs * (g[j][e] * gm[j][e] - s1 - x[j][e] * s2);
+        ag[j][e] = fmaf(g[j][e], x[j][e], ag[j][e]);
+        ab[j][e] += g[j][e];
+        ax[j][e] += o[e];
+      }
+      be_store4(dx + (int64_t)r * D + c, o);
+    }
+  }
+  for (int turn = 0; turn < 4; turn++) {  // waves 0, 1, 2, 3 in that order
+    if (w == turn) {
+#pragma unroll
+      for (int j = 0; j < BE_MAXJ; j++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const int c = (j * 64 + l) * 4 + e;
+          s_acc[0][c] = turn ? s_acc[0][c] + ag[j][e] : ag[j][e];
+          s_acc[1][c] = turn ? s_acc[1][c] + ab[j][e] : ab[j][e];
+          s_acc[2][c] = turn ? s_acc[2][c] + ax[j][e] : ax[j][e];
+        }
+    }
+    __syncthreads();
+  }
+  float* prow = part + (int64_t)blockIdx.x * 3 * D;
+  for (int c = threadIdx.x; c < D; c += 256) {
+    prow[c] = s_acc[0][c];
+    prow[D + c] = s_acc[1][c];
+    prow[2 * D + c] = s_acc[2][c];
+  }
+}
+
+// Backward, second kernel: a thread per column.  Workgroup row y < pos_rows: dpos[y][c] (=|+=) sum over b of dx[b][y][c] in the
+// order of b (zeros for y >= T); row y == pos_rows: dgamma, dbeta and the token-type row 0 from the first kernel's nblk
+// partial rows in their order, zeros into the token-type rows >= 1.
+__global__ __launch_bounds__(256) void bert_embeddings_bwd_reduce_kernel(
+    const float* __restrict__ dx, const float* __restrict__ part, int nblk, float* __restrict__ dpos, int64_t ld_dpos,
+    int pos_rows, float* __restrict__ dtype_tab, int64_t ld_dtype, int type_rows, float* __restrict__ dgamma,
+    float* __restrict__ dbeta, int B, int Tn, int D, int acc_pos, int acc_type, int acc_gamma, int acc_beta) {
+  const int c = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (c >= D) return;
+  if (y < pos_rows) {
+    if (y >= Tn && acc_pos) return;
+    float s = 0.f;
+    if (y < Tn) {
+      const float* p = dx + (int64_t)y * D + c;
+#pragma unroll 8
+      for (int b = 0; b < B; b++) s += p[(int64_t)b * Tn * D];
+    }
+    float* d = dpos + (int64_t)y * ld_dpos + c;
+    *d = acc_pos ? *d + s : s;
+    return;
+  }
+  float sg = 0.f, sb = 0.f, sx = 0.f;
+#pragma unroll 4
+  for (int i = 0; i < nblk; i++) {
+    const float* p = part + (int64_t)i * 3 * D + c;
+    sg += p[0];
+    sb += p[D];
+    sx += p[2 * D];
+  }
+  dgamma[c] = acc_gamma ? dgamma[c] + sg : sg;
+  dbeta[c] = acc_beta ? dbeta[c] + sb : sb;
+  dtype_tab[c] = acc_type ? dtype_tab[c] + sx : sx;
+  if (!acc_type)
+    for (int i = 1; i < type_rows; i++) dtype_tab[(int64_t)i * ld_dtype + c] = 0.f;
+}
+
 // y[i] = x[i] * keep(i) / (1 - p), flat element index i (forward and backward of an nn.Dropout call site)
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_apply_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n,
@@ -613,6 +831,54 @@ int embed_scatter(int dtype, const int64_t* tokens, const void* drows, int64_t l
   else { if (vec) OVQA_SCATTER(float, true); else OVQA_SCATTER(float, false); }
 #undef OVQA_SCATTER
   return ovqa_check_launch("embed_scatter");
+}
+
+int64_t bert_embeddings_bwd_blocks(int64_t R) { return (R + BE_BWD_ROWS - 1) / BE_BWD_ROWS; }
+
+int bert_embeddings_fwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab, const float* pos,
+                        int64_t ld_pos, const float* type0, const float* gamma, const float* beta, float eps, void* y,
+                        float* y32, float* mean, float* rstd, float* mask, int64_t mask_padding_idx, int64_t B, int64_t T,
+                        int64_t D, const DropArgs& da, hipStream_t st) {
+  const dim3 grid((unsigned)((B * T + 3) / 4)), block(256);
+  if (dtype == OVQA_BF16) {
+    OVQA_NOTE_LAUNCH(bert_embeddings_fwd_kernel<bf16>);
+    hipLaunchKernelGGL(bert_embeddings_fwd_kernel<bf16>, grid, block, 0, st, tokens, word, ld_word, vocab, pos, ld_pos, type0,
+                       gamma, beta, eps, (bf16*)y, y32, mean, rstd, mask, mask_padding_idx, (int)(B * T), (int)T, (int)D, da);
+  } else {
+    OVQA_NOTE_LAUNCH(bert_embeddings_fwd_kernel<float>);
+    hipLaunchKernelGGL(bert_embeddings_fwd_kernel<float>, grid, block, 0, st, tokens, word, ld_word, vocab, pos, ld_pos, type0,
+                       gamma, beta, eps, (float*)y, y32, mean, rstd, mask, mask_padding_idx, (int)(B * T), (int)T, (int)D, da);
+  }
+  return ovqa_check_launch("bert_embeddings_fwd");
+}
+
+int bert_embeddings_bwd(int dtype, const int64_t* tokens, const float* word, int64_t ld_word, int64_t vocab, const float* pos,
+                        int64_t ld_pos, const float* type0, const float* gamma, const float* mean, const float* rstd,
+                        const void* dy, float* dx, float* ws, float* dword, int64_t ld_dword, int64_t dword_rows,
+                        int64_t table_padding_idx, int acc_word, float* dpos, int64_t ld_dpos, int64_t dpos_rows, int acc_pos,
+                        float* dtype_tab, int64_t ld_dtype, int64_t dtype_rows, int acc_type, float* dgamma, int acc_gamma,
+                        float* dbeta, int acc_beta, int64_t B, int64_t T, int64_t D, const DropArgs& da, hipStream_t st) {
+  const int64_t R = B * T, nblk = bert_embeddings_bwd_blocks(R);
+  if (dtype == OVQA_BF16) {
+    OVQA_NOTE_LAUNCH(bert_embeddings_bwd_dx_kernel<bf16>);
+    hipLaunchKernelGGL(bert_embeddings_bwd_dx_kernel<bf16>, dim3((unsigned)nblk), dim3(256), 0, st, tokens, word, ld_word, vocab,
+                       pos, ld_pos, type0, gamma, mean, rstd, (const bf16*)dy, dx, ws, (int)R, (int)T, (int)D, da);
+  } else {
+    OVQA_NOTE_LAUNCH(bert_embeddings_bwd_dx_kernel<float>);
+    hipLaunchKernelGGL(bert_embeddings_bwd_dx_kernel<float>, dim3((unsigned)nblk), dim3(256), 0, st, tokens, word, ld_word,
+                       vocab, pos, ld_pos, type0, gamma, mean, rstd, (const float*)dy, dx, ws, (int)R, (int)T, (int)D, da);
+  }
+  int rc = ovqa_check_launch("bert_embeddings_bwd (dx)");
+  if (rc != OVQA_OK) return rc;
+  OVQA_NOTE_LAUNCH(bert_embeddings_bwd_reduce_kernel);
+  hipLaunchKernelGGL(bert_embeddings_bwd_reduce_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)(dpos_rows + 1)), dim3(256), 0,
+                     st, dx, ws, (int)nblk, dpos, ld_dpos, (int)dpos_rows, dtype_tab, ld_dtype, (int)dtype_rows, dgamma, dbeta,
+                     (int)B, (int)T, (int)D, acc_pos, acc_type, acc_gamma, acc_beta);
+  rc = ovqa_check_launch("bert_embeddings_bwd (reduce)");
+  if (rc != OVQA_OK) return rc;
+  // the word table: every row of it, rows no token names and row table_padding_idx as zeros (fixed order, no atomics)
+  OVQA_NOTE_LAUNCH((embed_scatter_kernel<float, true>));
+  return embed_scatter(OVQA_F32, tokens, dx, D, dword, ld_dword, dword_rows, B, T, D, 0, table_padding_idx, acc_word, st);
 }
 
 int dropout_apply(int dtype, const void* x, void* y, int64_t n, const DropArgs& da, hipStream_t st) {

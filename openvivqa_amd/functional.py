@@ -904,6 +904,64 @@ def embed_rows(tokens, emb, arena, time_major=False, master=False, want_mask=Fal
     return ops.embed_gather(tokens, arena.padded(emb.weight, st["buf"]), time_major, want_mask, pad)
 
 
+class _BertEmbeddings(Function):
+    """dropout(LN(word[tokens] + pos[:T] + type[0])) (transformers' BertEmbeddings as mmf_m4c.py:266-267 calls it) from the
+    fp32 master tables in one launch; backward: three launches that write the five gradients straight into the arena."""
+
+    @staticmethod
+    def forward(ctx, tokens, st, *params):
+        arena = st["arena"]
+        word, pos, typ, gamma, beta = st["params"]
+        T = arena.compute_dtype
+        y, y32, mean, rstd, st["_mask"] = ops.bert_embeddings_fwd(
+            tokens, arena.padded(word, "master"), arena.padded(pos, "master"), arena.padded(typ, "master"),
+            arena.master_of(gamma), arena.master_of(beta), st["eps"], out_dtype=T, drop=st["drop"],
+            want_f32=T == torch.bfloat16, mask_padding_idx=st["mask_padding_idx"], vocab=word.shape[0])
+        if y32 is not None:
+            st["_res_out"] = y32
+        ctx.st = st
+        ctx.save_for_backward(tokens, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        st = ctx.st
+        arena = st["arena"]
+        tokens, mean, rstd = ctx.saved_tensors
+        word, pos, typ, gamma, beta = st["params"]
+        views = [arena.grad_views([p]) for p in st["params"]]
+        ops.bert_embeddings_bwd(_c(dy), tokens, arena.padded(word, "master"), arena.padded(pos, "master"),
+                                arena.padded(typ, "master"), arena.master_of(gamma), mean, rstd,
+                                *(v for v, _ in views[:3]), views[3][0][:gamma.shape[0]], views[4][0][:beta.shape[0]],
+                                drop=st["drop"], table_padding_idx=st["table_padding_idx"],
+                                accumulate=[a for _, a in views], vocab=word.shape[0])
+        return (None, None) + (None,) * len(st["params"])
+
+
+def bert_embeddings(tokens, emb, arena, drop=None, mask_padding_idx=None):
+    """``emb`` (modules.mmt.BertEmbeddings) applied to int64 ``tokens`` [B, T] -> [B, T, D] in the compute dtype, the fp32
+    values attached as the residual twin in the bf16 mode; with ``mask_padding_idx`` also the (B, 1, 1, T) additive padding
+    mask of the ids, from the same launch: (y, mask)."""
+    word = emb.word_embeddings
+    params = [word.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight, emb.LayerNorm.weight,
+              emb.LayerNorm.bias]
+    st = dict(arena=arena, params=params, eps=emb.LayerNorm.eps, drop=drop, mask_padding_idx=mask_padding_idx,
+              table_padding_idx=word.padding_idx if word.padding_idx is not None else -1)
+    tokens = _c(tokens)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        y = _attach(_BertEmbeddings.apply(tokens, st, *params), st)
+    else:
+        y = _attach(_BertEmbeddings.forward(_NoGradCtx(), tokens, st), st)
+    return (y, st["_mask"]) if mask_padding_idx is not None else y
+
+
+class _NoGradCtx:
+    """Stand-in ``ctx`` for running a Function's forward without autograd."""
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
 class _Dropout(Function):
     @staticmethod
     def forward(ctx, x, drop):

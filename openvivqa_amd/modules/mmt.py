@@ -122,6 +122,105 @@ class BertEncoder(nn.Module):
         return (Fn.finalize(hidden_states, dtype),)
 
 
+class BertEmbeddings(nn.Module):
+    """transformers' ``BertEmbeddings`` as ``TextBert.forward`` calls it (mmf_m4c.py:266-267: ``self.embeddings(txt_inds)``,
+    no token types, no position ids): dropout(LayerNorm(word[ids] + token_type[0] + position[:T])) -- one HIP launch
+    (``ovqa_bert_embeddings_fwd``) from the fp32 master tables; its backward writes the five gradients (word table through
+    the deterministic per-token scatter) into the arena in three.  Same parameter names as transformers'; the config's
+    missing fields take transformers' defaults."""
+
+    def __init__(self, config):
+        super().__init__()
+        def cfg(name, default):
+            return getattr(config, name, default)
+        hidden = config.hidden_size
+        self.word_embeddings = nn.Embedding(cfg("vocab_size", 30522), hidden, padding_idx=cfg("pad_token_id", 0))
+        self.position_embeddings = nn.Embedding(cfg("max_position_embeddings", 512), hidden)
+        self.token_type_embeddings = nn.Embedding(cfg("type_vocab_size", 2), hidden)
+        self.LayerNorm = nn.LayerNorm(hidden, eps=cfg("layer_norm_eps", 1e-12))
+        self.dropout = nn.Dropout(cfg("hidden_dropout_prob", 0.1))
+        self._site = rt.new_dropout_site()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for name in ("position_ids", "token_type_ids"):  # buffers of transformers' module (persistent in old versions)
+            state_dict.pop(prefix + name, None)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, input_ids, mask_padding_idx=None):
+        """[B, T, hidden] in the compute dtype; with ``mask_padding_idx`` (the VOCABULARY's padding index) also the
+        (B, 1, 1, T) additive padding mask of the ids (generate_padding_mask, mmf_m4c.py:137-141) from the same launch."""
+        if input_ids.shape[1] > self.position_embeddings.num_embeddings:
+            raise RuntimeError(f"{input_ids.shape[1]} tokens per sample, {self.position_embeddings.num_embeddings} positions")
+        arena = rt.ensure_arena(self)
+        drop = rt.dropout_spec(self.dropout.p, self._site, self.training, input_ids.device)
+        return Fn.bert_embeddings(input_ids, self, arena, drop, mask_padding_idx)
+
+
+class TextBert(nn.Module):
+    """The reference's ``TextBert`` (mmf_m4c.py:258-279): BertEmbeddings + BertEncoder over the question tokens, with
+    transformers' parameter names (``embeddings.*``, ``encoder.layer.{i}.*``) and BERT's initialisation."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.embeddings = BertEmbeddings(config)
+        self.encoder = BertEncoder(config)
+        self.init_weights()
+
+    def init_weights(self):
+        """BertPreTrainedModel._init_weights: normal(0, initializer_range) matrices and tables, zero biases and padding row,
+        LayerNorm weight 1 / bias 0."""
+        std = getattr(self.config, "initializer_range", 0.02)
+        with torch.no_grad():
+            for m in self.modules():
+                if isinstance(m, nn.Linear):
+                    m.weight.normal_(0.0, std)
+                    m.bias.zero_()
+                elif isinstance(m, nn.Embedding):
+                    m.weight.normal_(0.0, std)
+                    if m.padding_idx is not None:
+                        m.weight[m.padding_idx].zero_()
+                elif isinstance(m, nn.LayerNorm):
+                    m.weight.fill_(1.0)
+                    m.bias.zero_()
+
+    def encode(self, txt_inds, padding_idx):
+        """(seq_output, txt_mask): the question mask comes out of the embeddings launch."""
+        x, txt_mask = self.embeddings(txt_inds, mask_padding_idx=padding_idx)
+        return self.encoder(x, txt_mask, head_mask=[None] * len(self.encoder.layer))[0], txt_mask
+
+    def forward(self, txt_inds, txt_mask):
+        x = self.embeddings(txt_inds)
+        return self.encoder(x, txt_mask, head_mask=[None] * len(self.encoder.layer))[0]
+
+
+def load_text_bert_weights(text_bert, path):
+    """TEXT_BERT.LOAD_PRETRAINED without a network: ``path`` is a local file holding a torch state dict, or a directory
+    holding one as ``pytorch_model.bin``.  Its ``[bert.]embeddings.*`` and ``[bert.]encoder.layer.{0..L-1}.*`` entries are
+    loaded; deeper layers, ``pooler.*`` and ``cls.*`` are dropped."""
+    import os
+    import re
+    if not isinstance(path, (str, os.PathLike)) or not os.path.exists(path):
+        raise RuntimeError(f"TEXT_BERT.PRETRAINED_NAME = {path!r} is not a local file or directory: pretrained weights are "
+                           "never downloaded, they must be supplied locally (a torch state dict)")
+    if os.path.isdir(path):
+        path = os.path.join(path, "pytorch_model.bin")
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} does not exist: pretrained weights must be supplied locally (a torch state dict)")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    n_layers = len(text_bert.encoder.layer)
+    keep = {}
+    for k, v in sd.items():
+        k = k[5:] if k.startswith("bert.") else k
+        m = re.match(r"encoder\.layer\.(\d+)\.", k)
+        if k.startswith("embeddings.") or (m is not None and int(m.group(1)) < n_layers):
+            keep[k] = v
+    missing, unexpected = text_bert.load_state_dict(keep, strict=False)
+    if missing or unexpected:
+        raise RuntimeError(f"{path}: missing {missing}, unexpected {unexpected}")
+    return text_bert
+
+
 class PrevPredEmbeddings(nn.Module):
     """Embeddings of the previous decoding steps' predictions (mmf_m4c.py:399-446): gather from
     [LN(fixed answer table); LN(OCR embeddings)] + LN(position + token-type embedding)."""

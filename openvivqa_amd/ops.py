@@ -1302,6 +1302,60 @@ def embed_scatter(tokens, drows, dtable, time_major=False, padding_idx=-1, accum
                                               int(padding_idx), int(bool(accumulate)), _stream()), "embed_scatter")
 
 
+def _bert_tables(tokens, word, pos, typ, gamma, vocab):
+    assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.is_contiguous() and tokens.is_cuda
+    for t in (word, pos, typ):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.is_cuda
+    assert gamma.dtype == torch.float32 and gamma.is_contiguous()
+    return int(vocab if vocab is not None else word.shape[0])
+
+
+def bert_embeddings_fwd(tokens, word, pos, typ, gamma, beta, eps=1e-12, out_dtype=torch.float32, drop=None, want_f32=False,
+                        mask_padding_idx=None, vocab=None):
+    """dropout(LN(word[tokens] + pos[:T] + typ[0])) in one launch (``ovqa_bert_embeddings_fwd``; transformers'
+    BertEmbeddings as mmf_m4c.py:266-267 calls it).  tokens int64 [B, T]; fp32 tables [rows, >= D] (row-strided views
+    allowed), ``vocab`` = the word rows a token may name (default: all of them); gamma / beta fp32 [D].  Returns
+    (y [B, T, D] of ``out_dtype``, y32 or None, mean, rstd, mask (B, 1, 1, T) or None)."""
+    _dev(word)
+    vocab = _bert_tables(tokens, word, pos, typ, gamma, vocab)
+    B, T = tokens.shape
+    D, dev = gamma.shape[0], word.device
+    y = torch.empty(B, T, D, dtype=out_dtype, device=dev)
+    y32 = torch.empty(B, T, D, dtype=torch.float32, device=dev) if want_f32 else None
+    mean = torch.empty(B * T, dtype=torch.float32, device=dev)
+    rstd = torch.empty(B * T, dtype=torch.float32, device=dev)
+    mask = torch.empty(B, 1, 1, T, dtype=torch.float32, device=dev) if mask_padding_idx is not None else None
+    _lib.check(_lib.load().ovqa_bert_embeddings_fwd(
+        _DT[out_dtype], _p(tokens), _p(word), word.stride(0), vocab, _p(pos), pos.stride(0), pos.shape[0], _p(typ), _p(gamma),
+        _p(beta), float(eps), _p(y), _p(y32), _p(mean), _p(rstd), _p(mask),
+        int(mask_padding_idx) if mask_padding_idx is not None else -1, B, T, D, _drop(drop), _stream()), "bert_embeddings_fwd")
+    return y, y32, mean, rstd, mask
+
+
+def bert_embeddings_bwd(dy, tokens, word, pos, typ, gamma, mean, rstd, dword, dpos, dtyp, dgamma, dbeta, drop=None,
+                        table_padding_idx=0, accumulate=(False,) * 5, vocab=None):
+    """Backward of ``bert_embeddings_fwd`` (``ovqa_bert_embeddings_bwd``: three launches, fixed summation order).  dy [B, T, D]
+    (fp32 or bf16); the five fp32 gradient buffers dword [>= vocab rows], dpos, dtyp, dgamma, dbeta are each stored or added to
+    as ``accumulate`` (word, pos, type, gamma, beta) says.  Returns dx, the fp32 gradient of the pre-LayerNorm sum."""
+    _dev(dy)
+    vocab = _bert_tables(tokens, word, pos, typ, gamma, vocab)
+    B, T = tokens.shape
+    D = gamma.shape[0]
+    assert dy.is_contiguous() and dy.numel() == B * T * D
+    for g in (dword, dpos, dtyp):
+        assert g.dtype == torch.float32 and g.dim() == 2 and g.stride(1) == 1
+    assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.is_contiguous() and dbeta.is_contiguous()
+    dx = torch.empty(B * T, D, dtype=torch.float32, device=dy.device)
+    ws = torch.empty(((B * T + 7) // 8) * 3 * D, dtype=torch.float32, device=dy.device)
+    a = [int(bool(v)) for v in accumulate]
+    _lib.check(_lib.load().ovqa_bert_embeddings_bwd(
+        _dt(dy), _p(tokens), _p(word), word.stride(0), vocab, _p(pos), pos.stride(0), pos.shape[0], _p(typ), _p(gamma),
+        _p(mean), _p(rstd), _p(dy), _p(dx), _p(ws), ws.numel(), _p(dword), dword.stride(0), dword.shape[0],
+        int(table_padding_idx), a[0], _p(dpos), dpos.stride(0), dpos.shape[0], a[1], _p(dtyp), dtyp.stride(0), dtyp.shape[0],
+        a[2], _p(dgamma), a[3], _p(dbeta), a[4], B, T, D, _drop(drop), _stream()), "bert_embeddings_bwd")
+    return dx
+
+
 def decoder_inputs(tokens, emb, pos_table, padding_idx):
     """(emb + pos_table[seq], self_mask [B, 1, T, T]) of a teacher-forced decoder pass in one launch
     (``ovqa_decoder_inputs``; decoders.py:50-60,66).  tokens int64 [B, T]; emb fp32 [B, T, D]; pos_table fp32 [>= T + 1, D]."""
