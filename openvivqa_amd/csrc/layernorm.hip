@@ -372,6 +372,7 @@ int fwd_dispatch(const void* x, const float* gamma, const float* beta, const flo
                  float* y32, float* mean, float* rstd, int64_t M, int64_t D, float eps, hipStream_t st) {
   const int chunks = (int)((D + 64 * VEC - 1) / (64 * VEC));
 #define LN_FWD_RW(C, R, NW)                                                                                          \
+  OVQA_NOTE_LAUNCH((ln_fwd_kernel<TIN, TOUT, C, R, NW>));                                                            \
   hipLaunchKernelGGL((ln_fwd_kernel<TIN, TOUT, C, R, NW>), dim3((unsigned)((M + R * NW - 1) / (R * NW))),            \
                      dim3(NW * 64), 0, st, (const TIN*)x, gamma, beta, pos, (int)(pos ? pos_rows : 1), (TOUT*)y, y32, \
                      mean, rstd, (int)M, (int)D, eps)
@@ -395,11 +396,12 @@ int bwd_dispatch(const void* dy, const void* x, const float* gamma, const float*
   float* partial = (float*)ws;
   const size_t smem = (size_t)(nw - 1) * 2 * D * sizeof(float);
 #define LN_BWD_W(C, W)                                                                                              \
+  OVQA_NOTE_LAUNCH((ln_bwd_kernel<TDY, TX, TDX, C, W>));                                                            \
   hipLaunchKernelGGL((ln_bwd_kernel<TDY, TX, TDX, C, W>), dim3(nblocks), dim3(W * 64), smem, st, (const TDY*)dy,    \
                      (const TX*)x, gamma, mean, rstd, (TDX*)dx, (TDY*)dx_dropped, partial, (int)M, (int)D, da)
 #define LN_BWD(C)                                                                                                   \
-  if (nw == 8) LN_BWD_W(C, 8);                                                                                      \
-  else LN_BWD_W(C, 4);
+  if (nw == 8) { LN_BWD_W(C, 8); }                                                                                  \
+  else { LN_BWD_W(C, 4); }
   switch (chunks) {
     case 1: LN_BWD(1); break;
     case 2: LN_BWD(2); break;

@@ -904,11 +904,12 @@ int pool_fwd(int feat_dtype, int dtype, const void* feat, const void* hpre, cons
                "pool_fwd: 16-byte alignment");
   const dim3 grid((unsigned)B), block(POOL_WAVES * 64);
 #define OVQA_POOL_FWD(F, T)                                                                                             \
+  OVQA_NOTE_LAUNCH((pool_fwd_kernel<F, T>));                                                                            \
   hipLaunchKernelGGL((pool_fwd_kernel<F, T>), grid, block, 0, st, (const F*)feat, (const T*)hpre, w2, b2, att, (T*)pooled, \
                      pooled32, (int)N, (int)D, da)
-  if (dtype == OVQA_BF16 && feat_dtype == OVQA_BF16) OVQA_POOL_FWD(bf16, bf16);
-  else if (dtype == OVQA_BF16) OVQA_POOL_FWD(float, bf16);
-  else if (feat_dtype == OVQA_F32) OVQA_POOL_FWD(float, float);
+  if (dtype == OVQA_BF16 && feat_dtype == OVQA_BF16) { OVQA_POOL_FWD(bf16, bf16); }
+  else if (dtype == OVQA_BF16) { OVQA_POOL_FWD(float, bf16); }
+  else if (feat_dtype == OVQA_F32) { OVQA_POOL_FWD(float, float); }
   else { ovqa_set_error("pool_fwd: bf16 features with fp32 hidden activations"); return OVQA_ERR_UNSUPPORTED; }
 #undef OVQA_POOL_FWD
   return ovqa_check_launch("pool_fwd");
@@ -920,11 +921,12 @@ int pool_bwd(int feat_dtype, int dtype, const void* feat, const void* hpre, cons
   OVQA_REQUIRE(pool_shape_ok(N, D), OVQA_ERR_UNSUPPORTED, "pool_bwd: N <= 1024, D <= 1024, D %% 8 == 0");
   const dim3 grid((unsigned)B), block(POOL_WAVES * 64);
 #define OVQA_POOL_BWD(F, T)                                                                                              \
+  OVQA_NOTE_LAUNCH((pool_bwd_kernel<F, T>));                                                                             \
   hipLaunchKernelGGL((pool_bwd_kernel<F, T>), grid, block, 0, st, (const F*)feat, (const T*)hpre, w2, att, (const T*)dpooled, (T*)dh, \
                      (T*)dfeat, dw2_part, db2_part, (int)N, (int)D, da)
-  if (dtype == OVQA_BF16 && feat_dtype == OVQA_BF16) OVQA_POOL_BWD(bf16, bf16);
-  else if (dtype == OVQA_BF16) OVQA_POOL_BWD(float, bf16);
-  else if (feat_dtype == OVQA_F32) OVQA_POOL_BWD(float, float);
+  if (dtype == OVQA_BF16 && feat_dtype == OVQA_BF16) { OVQA_POOL_BWD(bf16, bf16); }
+  else if (dtype == OVQA_BF16) { OVQA_POOL_BWD(float, bf16); }
+  else if (feat_dtype == OVQA_F32) { OVQA_POOL_BWD(float, float); }
   else { ovqa_set_error("pool_bwd: bf16 features with fp32 hidden activations"); return OVQA_ERR_UNSUPPORTED; }
 #undef OVQA_POOL_BWD
   return ovqa_check_launch("pool_bwd");
@@ -937,37 +939,45 @@ static bool lsm_rows(int dtype, const void* x, int64_t ld, const void* f32a, con
          (uintptr_t)f32a % 16 == 0 && (uintptr_t)f32b % 16 == 0;
 }
 
+// (the launch log names the form: a test can say whether a shape ran the row or the wave kernel)
+#define OVQA_LSM_LAUNCH(kernel, grid, block, lds, st, ...)          \
+  do {                                                             \
+    OVQA_NOTE_LAUNCH(kernel);                                      \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__); \
+  } while (0)
+
 int log_softmax_fwd(int dtype, const void* x, int64_t ld, float* out, int64_t M, int64_t n, hipStream_t st) {
   if (lsm_rows(dtype, x, ld, out, nullptr, n)) {
     if (dtype == OVQA_BF16)
-      hipLaunchKernelGGL(log_softmax_fwd_row_kernel<bf16>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, (const bf16*)x, ld, out, (int)n);
+      OVQA_LSM_LAUNCH(log_softmax_fwd_row_kernel<bf16>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, (const bf16*)x, ld, out, (int)n);
     else
-      hipLaunchKernelGGL(log_softmax_fwd_row_kernel<float>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, (const float*)x, ld, out, (int)n);
+      OVQA_LSM_LAUNCH(log_softmax_fwd_row_kernel<float>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, (const float*)x, ld, out, (int)n);
     return ovqa_check_launch("log_softmax_fwd");
   }
   const unsigned grid = (unsigned)((M + 3) / 4);
   if (dtype == OVQA_BF16)
-    hipLaunchKernelGGL(log_softmax_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x, ld, out, (int)M, (int)n);
+    OVQA_LSM_LAUNCH(log_softmax_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x, ld, out, (int)M, (int)n);
   else
-    hipLaunchKernelGGL(log_softmax_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, ld, out, (int)M, (int)n);
+    OVQA_LSM_LAUNCH(log_softmax_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, ld, out, (int)M, (int)n);
   return ovqa_check_launch("log_softmax_fwd");
 }
 
 int log_softmax_bwd(int dtype, const float* g, const float* logp, void* dx, int64_t ld, int64_t M, int64_t n, hipStream_t st) {
   if (lsm_rows(dtype, dx, ld, g, logp, n)) {
     if (dtype == OVQA_BF16)
-      hipLaunchKernelGGL(log_softmax_bwd_row_kernel<bf16>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, g, logp, (bf16*)dx, ld, (int)n);
+      OVQA_LSM_LAUNCH(log_softmax_bwd_row_kernel<bf16>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, g, logp, (bf16*)dx, ld, (int)n);
     else
-      hipLaunchKernelGGL(log_softmax_bwd_row_kernel<float>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, g, logp, (float*)dx, ld, (int)n);
+      OVQA_LSM_LAUNCH(log_softmax_bwd_row_kernel<float>, dim3((unsigned)M), dim3(LSM_THREADS), 0, st, g, logp, (float*)dx, ld, (int)n);
     return ovqa_check_launch("log_softmax_bwd");
   }
   const unsigned grid = (unsigned)((M + 3) / 4);
   if (dtype == OVQA_BF16)
-    hipLaunchKernelGGL(log_softmax_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, g, logp, (bf16*)dx, ld, (int)M, (int)n);
+    OVQA_LSM_LAUNCH(log_softmax_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, g, logp, (bf16*)dx, ld, (int)M, (int)n);
   else
-    hipLaunchKernelGGL(log_softmax_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, g, logp, (float*)dx, ld, (int)M, (int)n);
+    OVQA_LSM_LAUNCH(log_softmax_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, g, logp, (float*)dx, ld, (int)M, (int)n);
   return ovqa_check_launch("log_softmax_bwd");
 }
+#undef OVQA_LSM_LAUNCH
 
 int nll_loss(const float* logp, const int64_t* target, float* loss, float* dlogp, const float* gscale, int64_t M, int64_t n,
              int64_t ignore_index, int accumulate, hipStream_t st) {
@@ -975,6 +985,7 @@ int nll_loss(const float* logp, const int64_t* target, float* loss, float* dlogp
   int rows_per_wg = 4;
   while ((M + rows_per_wg - 1) / rows_per_wg > 4096) rows_per_wg *= 2;
   const unsigned grid = dlogp ? (unsigned)std::max<int64_t>(1, (M + rows_per_wg - 1) / rows_per_wg) : 1u;
+  OVQA_NOTE_LAUNCH(nll_loss_kernel);
   hipLaunchKernelGGL(nll_loss_kernel, dim3(grid), dim3(256), 0, st, logp, target, loss, dlogp, gscale, (int)M, (int)n,
                      ignore_index, accumulate, rows_per_wg);
   return ovqa_check_launch("nll_loss");
