@@ -71,8 +71,8 @@ __device__ __forceinline__ void wg_role(int b, int nsg, int& sg, int& ub) {
 }
 
 // ---- the hand-off: the data is the flag ------------------------------------------------------------------
-// The exchange buffer is filled with 0xFF bytes by a memset node in front of the launch: 0xFFFF is a bf16 NaN that neither
-// h = o tanh(c) nor a finite gradient can be.  A consumer wave simply re-reads its 16 KB with sc1 loads until no 8-byte
+// The exchange buffer is filled with 0xFF bytes by lstm_sentinel_fill_kernel in front of the launch: 0xFFFF is a bf16 NaN that
+// neither h = o tanh(c) nor a finite gradient can be.  A consumer wave simply re-reads its 16 KB with sc1 loads until no 8-byte
 // unit shows the sentinel (cdna_hip_programming.md Guideline 16, recipe R2: 8-byte granules written by ONE sc1 store are
 // observed untorn; here the tag is "not 0xFFFF" in the unit's first element, so the payload is not doubled).  Against
 // the counter form this drops, per step: the producer's store drain, the atomic, the poll round trip and a workgroup
@@ -100,6 +100,18 @@ __device__ __forceinline__ void sweep_until_ready(const RS& rs, unsigned off, u3
     }
     __builtin_amdgcn_s_sleep(1);
   }
+}
+
+// The sentinel fill, as a kernel of this library in front of the persistent launch (16-byte vector stores; both exchange
+// buffers are 16-byte aligned multiples of 16 bytes).  It was a hipMemsetAsync node until the graph-replay test of
+// tests/test_lstm_routes_gpu.py: a captured lstm_fwd + lstm_bwd at B = 16, T = 3 replayed on NEW inputs read, from the third
+// time step on, h / dgates values of the previous replay as ready.  MEASURED on the MI355X with a captured hipMemsetAsync
+// followed by a copy kernel: on replay the memset node of a 64 KiB buffer wrote 4 KiB of it and that of a 192 KiB buffer
+// nothing (1.3 MiB: all of it), and what the previous replay left in the same buffer is no sentinel.  Replays on the SAME
+// inputs are bit-identical either way, which is why no earlier test saw it; a kernel node does not depend on that path.
+__global__ __launch_bounds__(256) void lstm_sentinel_fill_kernel(u32x4* __restrict__ p, int64_t n16) {
+  const u32x4 v = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) p[i] = v;
 }
 
 struct LstmFwdArgs {
@@ -479,6 +491,13 @@ int device_cus() {
   return cus;
 }
 
+void sentinel_fill(void* p, int64_t bytes, hipStream_t st) {  // bytes: a multiple of 16 (rows of 512 / 2048 bf16)
+  const int64_t n16 = bytes / 16;
+  OVQA_NOTE_LAUNCH(lstm_sentinel_fill_kernel);
+  hipLaunchKernelGGL(lstm_sentinel_fill_kernel, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 1024)), dim3(256), 0, st,
+                     (u32x4*)p, n16);
+}
+
 constexpr int kSyncBytes = 4096;                 // counters (one 128-byte line per sample group) + status word
 constexpr int kPersistentLds = 96 * 1024;        // more than half a CU's LDS: one workgroup per CU
 
@@ -519,9 +538,8 @@ int lstm_fwd(int dtype, bool persistent, const void* x, int64_t ldx, const void*
              const float* b_ih, const float* b_hh, float* y, void* y16, void* hseq, void* saved, void* scratch, int64_t B, int64_t T,
              int64_t I, int64_t H, hipStream_t st) {
   if (persistent) {
-    // ONE memset node, the sentinel fill (the status word is zeroed by the launch's first workgroup)
-    hipError_t e = hipMemsetAsync(hseq, 0xFF, (size_t)((T + 1) * B * LH * 2), st);
-    OVQA_REQUIRE(e == hipSuccess, OVQA_ERR_LAUNCH, "lstm_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
+    // the sentinel fill (the status word is zeroed by the launch's first workgroup)
+    sentinel_fill(hseq, (T + 1) * B * LH * 2, st);
     LstmFwdArgs a{(const bf16*)x, ldx, (const bf16*)w_ih, (const bf16*)w_hh, b_ih, b_hh, y, (bf16*)y16, (bf16*)hseq, (float*)saved,
                   (unsigned*)scratch + 1000, (int)B, (int)T,
                   debug_env("OVQA_LSTM_SWEEP_LIMIT", SWEEP_LIMIT), debug_env("OVQA_LSTM_DEBUG_DROP_WG", 0),
@@ -532,6 +550,7 @@ int lstm_fwd(int dtype, bool persistent, const void* x, int64_t ldx, const void*
                                 kPersistentLds);
       attr_set = true;
     }
+    OVQA_NOTE_LAUNCH(lstm_fwd_persistent_kernel);
     hipLaunchKernelGGL(lstm_fwd_persistent_kernel, dim3((unsigned)((B / 16) * NUB)), dim3(256), kPersistentLds, st, a);
     return ovqa_check_launch("lstm_fwd(persistent)");
   }
@@ -539,13 +558,16 @@ int lstm_fwd(int dtype, bool persistent, const void* x, int64_t ldx, const void*
   float* cs = gates + T * B * 4 * H;
   const int blocks = (int)((B * H + 255) / 256);
   for (int t = 0; t < T; t++) {
-    if (dtype == OVQA_BF16)
+    if (dtype == OVQA_BF16) {
+      OVQA_NOTE_LAUNCH(lstm_step_fwd_simple<bf16>);
       hipLaunchKernelGGL(lstm_step_fwd_simple<bf16>, dim3(blocks), dim3(256), 0, st, (const bf16*)x, ldx, (const bf16*)w_ih,
                          b_ih, (const bf16*)w_hh, b_hh, (bf16*)hseq, y, (bf16*)y16, gates, cs, (int)B, (int)T, (int)I, (int)H, t);
-    else
+    } else {
+      OVQA_NOTE_LAUNCH(lstm_step_fwd_simple<float>);
       hipLaunchKernelGGL(lstm_step_fwd_simple<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, ldx,
                          (const float*)w_ih, b_ih, (const float*)w_hh, b_hh, (float*)hseq, y, (float*)y16, gates, cs, (int)B,
                          (int)T, (int)I, (int)H, t);
+    }
   }
   return ovqa_check_launch("lstm_fwd(simple)");
 }
@@ -553,8 +575,7 @@ int lstm_fwd(int dtype, bool persistent, const void* x, int64_t ldx, const void*
 int lstm_bwd(int dtype, bool persistent, const void* dy, int dy_bf16, const void* w_hh, const void* w_hh_t, int64_t ldwt,
              const void* saved, void* dgates, void* scratch, int64_t B, int64_t T, int64_t H, hipStream_t st) {
   if (persistent) {
-    hipError_t e = hipMemsetAsync(dgates, 0xFF, (size_t)(T * B * 4 * LH * 2), st);
-    OVQA_REQUIRE(e == hipSuccess, OVQA_ERR_LAUNCH, "lstm_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
+    sentinel_fill(dgates, T * B * 4 * LH * 2, st);
     LstmBwdArgs a{dy, dy_bf16, (const bf16*)w_hh_t, ldwt, (const float*)saved, (bf16*)dgates,
                   (unsigned*)scratch + 1000, (int)B, (int)T, debug_env("OVQA_LSTM_SWEEP_LIMIT", SWEEP_LIMIT),
                   debug_env("OVQA_LSTM_DEBUG_DROP_WG", 0)};
@@ -564,6 +585,7 @@ int lstm_bwd(int dtype, bool persistent, const void* dy, int dy_bf16, const void
                                 kPersistentLds);
       attr_set = true;
     }
+    OVQA_NOTE_LAUNCH(lstm_bwd_persistent_kernel);
     hipLaunchKernelGGL(lstm_bwd_persistent_kernel, dim3((unsigned)((B / 16) * NUB)), dim3(256), kPersistentLds, st, a);
     return ovqa_check_launch("lstm_bwd(persistent)");
   }
@@ -572,12 +594,15 @@ int lstm_bwd(int dtype, bool persistent, const void* dy, int dy_bf16, const void
   float* carry = (float*)((unsigned char*)scratch + kSyncBytes);
   const int blocks = (int)((B * H + 255) / 256);
   for (int t = (int)T - 1; t >= 0; t--) {
-    if (dtype == OVQA_BF16)
+    if (dtype == OVQA_BF16) {
+      OVQA_NOTE_LAUNCH(lstm_step_bwd_simple<bf16>);
       hipLaunchKernelGGL(lstm_step_bwd_simple<bf16>, dim3(blocks), dim3(256), 0, st, dy, dy_bf16, (const bf16*)w_hh, gates, cs,
                          (bf16*)dgates, carry, (int)B, (int)T, (int)H, t);
-    else
+    } else {
+      OVQA_NOTE_LAUNCH(lstm_step_bwd_simple<float>);
       hipLaunchKernelGGL(lstm_step_bwd_simple<float>, dim3(blocks), dim3(256), 0, st, dy, dy_bf16, (const float*)w_hh, gates, cs,
                          (float*)dgates, carry, (int)B, (int)T, (int)H, t);
+    }
   }
   return ovqa_check_launch("lstm_bwd(simple)");
 }
