@@ -14,6 +14,8 @@
 // ds_read_b128 operand reads AND the transposing reads of the same [rows][64] image bank-conflict free.
 // Small problems are packed: a workgroup's 4 waves cover ceil(nq/32) query tiles of 4/W different
 // (batch, head) pairs, so the 20-token question stack still fills its waves.
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -36,6 +38,7 @@ extern "C" int ovqa_debug_probe(unsigned long long* out) {
 #endif
 
 #include "attention_frags.h"
+#include "attention_project.h"
 
 namespace {
 
@@ -293,7 +296,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(ovqa::AttnArgs a, in
 // ------------------------------------------------------------------------- fused Q/K/V projection + attention
 // Self-attention forward with the projections inside (hard part 1): a workgroup owns S samples of
 // ONE head -- x rows [S * RP][512] against the head's 192 weight rows (64 of fc_q, fc_k, fc_v each) -- computes
-// Q | K | V = x W_h^T + b with a GEMM main loop like gemm_mfma.hip's (v_mfma_f32_16x16x32_bf16, direct-to-LDS ring of
+// Q | K | V = x W_h^T + b with the projection loop of attention_project.h (v_mfma_f32_16x16x32_bf16, direct-to-LDS ring of
 // four 32-deep K tiles, XOR-swizzled [rows][32] images, weight rows staged in the permuted order that gives a lane 8
 // consecutive output features), stores the bf16 projections BOTH to HBM (backward needs them) and into the LDS images the
 // attention core reads, and runs that core on them: the projected Q, K, V are never re-read from HBM, the separate
@@ -302,8 +305,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(ovqa::AttnArgs a, in
 //   M = S * RP = 128 or 256 GEMM rows per workgroup, 8 waves as 4 (rows) x 2 (features): NI = M / 64 row units x 6
 //   feature units of 16 per wave.  Attention: wave w takes query tile w % (RP/32) of sample w / (RP/32).
 __device__ __forceinline__ int perm32(int t) { return (t & ~31) | ((t & 12) << 1) | (((t >> 4) & 1) << 2) | (t & 3); }
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 struct QkvAttnArgs {
   const bf16* x; int64_t ldx;       // [B * n, Dm]
@@ -318,16 +319,10 @@ struct QkvAttnArgs {
 // and with two workgroups per CU (scripts/lds_stream_probe.py: 105 GB/s per CU against 64-71), which is what the
 // 128-row single-sample form <128, 1, 64, 2> buys (80 KiB of LDS: two workgroups per CU, the attention of one under the
 // projection of the other) at the price of streaming the head's weights once per sample instead of once per pair.
+template <int RP, int S, int BKF, int NBUF> using QkvProj = ProjLoop<6, RP * S / 64, BKF, NBUF, 8, 192, RP * S>;
 template <int RP, int S, bool ROWMASK, int BKF = 32, int NBUF = 4>
 __global__ __launch_bounds__(512) void attn_qkv_fwd_mfma_kernel(QkvAttnArgs g) {
   constexpr int M = RP * S, NI = M / 64, NJ = 6, NKT = RP / 32, TQ = RP / 32;
-  constexpr int PROWS = 1024 / (BKF * 2);            // rows of a 1 KiB staging piece: 16 (64-B rows) or 8 (128-B rows)
-  constexpr int CHR = BKF / 8;                       // 16-byte chunks per row: 4 or 8
-  constexpr int WCH = 192 / PROWS, XCH = M / PROWS;  // pieces of the W / x tiles
-  constexpr int PCS = WCH + XCH;                     // pieces per stage
-  constexpr int PER = (PCS + 7) / 8;                 // per wave: PER pieces, the last one only for waves < PCS - 8 * (PER - 1)
-  constexpr int FULL = PCS - 8 * (PER - 1);          // waves with PER pieces
-  constexpr int STAGE = PCS * 1024;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ovqa::AttnArgs& a = g.att;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -335,36 +330,27 @@ __global__ __launch_bounds__(512) void attn_qkv_fwd_mfma_kernel(QkvAttnArgs g) {
   const int h = blockIdx.y, b0 = blockIdx.x * S, n = a.nq, HD = a.H * 64;
 
   f32x4 acc[NJ][NI];
+  // This kernel fills the loop's source pointers itself, with setup()'s code: through setup()'s callables the same
+  // arithmetic reaches the register allocator in another order and costs 2-10 VGPRs (<64, 4, true, 32, 4>: 167 -> 173-177,
+  // one wave per SIMD less by the register count; <32, 4, true, 32, 4>: 113 -> 115-119)
+  using Proj = QkvProj<RP, S, BKF, NBUF>;
+  Proj pl;
+  Proj::zero(acc);
 #pragma unroll
-  for (int j = 0; j < NJ; j++)
-#pragma unroll
-    for (int i = 0; i < NI; i++) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // [rows][32] bf16 image, 64 B per row: chunk ch of row r sits in 16-byte slot ch ^ g((r >> 2) & 3), g = {0, 2, 3, 1}.
-  // ds_read_b128 serves the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS): with
-  // lane -> (row base + (lane & 15), chunk lane >> 4) a group holds rows {0-3, 12-15} of one chunk and rows {4-11} of
-  // the next, and this g puts their 16 slots on 16 distinct 16-byte bank columns (the plain (r >> 2) & 3 is 2-way
-  // conflicting: 1.5 M conflict cycles per launch).  A staging piece is 16 rows = 1 KiB; lane l of the loading wave
-  // fills slot l & 3 of row l >> 2, i.e. fetches global chunk (l & 3) ^ g.
-  // (128-byte rows, BKF = 64: the GEMM kernels' slot = chunk ^ (row & 7))
-  auto swz = [](int row) { return BKF == 32 ? (0x78 >> (2 * ((row >> 2) & 3))) & 3 : (row & 7); };
-  auto off32 = [&](int row, int ch) { return row * (BKF * 2) + ((ch ^ swz(row)) << 4); };
-  const bf16* src[PER];  // this lane's source row (+ chunk) of each of its pieces, K offset 0
-#pragma unroll
-  for (int i = 0; i < PER; i++) {
+  for (int i = 0; i < Proj::PER; i++) {
     const int ci = wave + 8 * i;
-    const int prow = lane / CHR, pch = lane % CHR;
-    if (ci < WCH) {  // weight rows of this head: tile row t -> kind t/64 (q, k, v), feature t%64, permuted within 32
-      const int row = ci * PROWS + prow;
+    const int prow = lane / Proj::CHR, pch = lane % Proj::CHR;
+    if (ci < Proj::WCH) {  // weight rows of this head: tile row t -> kind t/64 (q, k, v), feature t%64, permuted within 32
+      const int row = ci * Proj::PROWS + prow;
       const int t = perm32(row);
-      src[i] = g.w + (int64_t)((t >> 6) * HD + h * 64 + (t & 63)) * g.Dm + ((pch ^ swz(row)) << 3);
-    } else {         // x rows: sample (row / RP), position clamped to the sample's last row
-      const int row = (ci - WCH) * PROWS + prow;
+      pl.src[i] = g.w + (int64_t)((t >> 6) * HD + h * 64 + (t & 63)) * g.Dm + ((pch ^ Proj::swz(row)) << 3);
+    } else {               // x rows: sample (row / RP), position clamped to the sample's last row
+      const int row = (ci - Proj::WCH) * Proj::PROWS + prow;
       int bs = b0 + row / RP;
       bs = bs < a.B ? bs : a.B - 1;
       int r = row % RP;
       r = r < n ? r : n - 1;
-      src[i] = g.x + ((int64_t)bs * n + r) * g.ldx + ((pch ^ swz(row)) << 3);
+      pl.src[i] = g.x + ((int64_t)bs * n + r) * g.ldx + ((pch ^ Proj::swz(row)) << 3);
     }
   }
   // the epilogue's bias values (8 consecutive features per (jp) of this lane), requested before the K loop
@@ -376,48 +362,8 @@ __global__ __launch_bounds__(512) void attn_qkv_fwd_mfma_kernel(QkvAttnArgs g) {
     bias_r[jp][0] = g.bias ? *reinterpret_cast<const float4*>(g.bias + gcol) : make_float4(0.f, 0.f, 0.f, 0.f);
     bias_r[jp][1] = g.bias ? *reinterpret_cast<const float4*>(g.bias + gcol + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  const bool full = wave < FULL;  // wave-uniform
-  auto issue = [&](int kt) {
-    char* buf = smem + (kt % NBUF) * STAGE;
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      if (i == PER - 1 && !full) break;
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src[i] + kt * BKF), (lds_void*)(buf + (wave + 8 * i) * 1024), 16, 0, 0);
-    }
-  };
-  const int nkt = g.Dm / BKF;
   OVQA_PROBE(0);
-#pragma unroll
-  for (int p = 0; p < NBUF - 1; p++)
-    if (p < nkt) issue(p);
-  for (int kt = 0; kt < nkt; kt++) {
-    // stage kt has landed once at most the loads of the two younger stages are outstanding (in-order return)
-    if (kt + NBUF - 2 >= nkt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (full) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NBUF - 2)) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PER - 1) * (NBUF - 2)) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (kt + NBUF - 1 < nkt) issue(kt + NBUF - 1);
-    const char* Ws = smem + (kt % NBUF) * STAGE;
-    const char* Xs = Ws + WCH * 1024;
-#pragma unroll
-    for (int ks = 0; ks < BKF / 32; ks++) {
-      bf16x8 pf[NJ], qf[NI];
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-        pf[j] = *reinterpret_cast<const bf16x8*>(Ws + off32(wr * 96 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int i = 0; i < NI; i++)
-        qf[i] = *reinterpret_cast<const bf16x8*>(Xs + off32(wc * (NI * 16) + i * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-#pragma unroll
-        for (int i = 0; i < NI; i++) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[j], qf[i], acc[j][i], 0, 0, 0);
-    }
-  }
+  pl.run(acc, smem, wave, lane, wr, wc, g.Dm / BKF);
   OVQA_PROBE(1);
   __syncthreads();  // every wave is done with the staging buffers: they become the Q | K | V images
   OVQA_PROBE(2);
@@ -435,12 +381,7 @@ __global__ __launch_bounds__(512) void attn_qkv_fwd_mfma_kernel(QkvAttnArgs g) {
     for (int jp = 0; jp < NJ / 2; jp++) {
       const int f = wr * 96 + jp * 32 + (lane >> 4) * 8;  // 8 consecutive features of one of q / k / v
       const int kind = f >> 6, col = f & 63;
-      const float4 c0 = bias_r[jp][0], c1 = bias_r[jp][1];
-      bf16x8 o8;
-      o8[0] = (bf16)(acc[2 * jp][i][0] + c0.x); o8[1] = (bf16)(acc[2 * jp][i][1] + c0.y);
-      o8[2] = (bf16)(acc[2 * jp][i][2] + c0.z); o8[3] = (bf16)(acc[2 * jp][i][3] + c0.w);
-      o8[4] = (bf16)(acc[2 * jp + 1][i][0] + c1.x); o8[5] = (bf16)(acc[2 * jp + 1][i][1] + c1.y);
-      o8[6] = (bf16)(acc[2 * jp + 1][i][2] + c1.z); o8[7] = (bf16)(acc[2 * jp + 1][i][3] + c1.w);
+      const bf16x8 o8 = pack_bias8(acc[2 * jp][i], acc[2 * jp + 1][i], bias_r[jp][0], bias_r[jp][1]);
       *reinterpret_cast<bf16x8*>(smem + ((sm * 3 + kind) * RP) * 128 + Img<64>::off(r, col >> 3)) = o8;
       if (live) *reinterpret_cast<bf16x8*>(grow + kind * HD + col) = o8;
     }
@@ -471,7 +412,7 @@ __global__ __launch_bounds__(512) void attn_qkv_fwd_mfma_kernel(QkvAttnArgs g) {
 // ------------------------------------------------------------------------- fused Q projection + attention (round 3)
 // Cross / guided attention forward with the QUERY projection inside: the keys and values are already projected (the
 // hoisted K / V GEMM of the guided stack, or a packed K | V projection), only q = x W_q^T + b_q is computed here -- the
-// main loop of attn_qkv_fwd_mfma_kernel on 64 weight rows instead of 192 -- stored to HBM (backward reads it) and into
+// shared projection loop (ProjLoop) on 64 weight rows instead of attn_qkv_fwd_mfma_kernel's 192 -- stored to HBM (backward reads it) and into
 // the LDS image the attention core reads; K / V of the head (NKT * 32 padded keys) are staged next to it.  One launch
 // instead of a 6400 x 512 <- 512 GEMM + the attention kernel, and q is not re-read.
 // RP = 128 query rows of ONE sample per workgroup (8 waves as 4 (rows) x 2 (features): 32 x 32 per wave), K steps of 64,
@@ -487,82 +428,30 @@ struct QAttnArgs {
 
 // NH = heads per workgroup (1: 8 waves; 2: 16 waves, the x rows are staged ONCE for both heads -- 32 instead of 48 KB per
 // K step through the CU's fetch path -- and 64 samples x 4 head pairs are exactly one workgroup per CU).
+template <int NBUF, int NH> using QProj = ProjLoop<2, 2, 64, NBUF, 8 * NH, 64 * NH, 128>;
 template <int NKT, int NBUF, int NH>
 __global__ __launch_bounds__(512 * NH) void attn_q_fwd_mfma_kernel(QAttnArgs g) {
-  constexpr int RP = 128, BKF = 64, NI = 2, NJ = 2, TQ = RP / 32, KP = NKT * 32, NW = 8 * NH;
-  constexpr int PROWS = 8, CHR = 8;                       // a 1 KiB staging piece = 8 rows of 128 B
-  constexpr int WCH = 64 * NH / PROWS, XCH = RP / PROWS;  // weight / x pieces per stage
-  constexpr int PER = (WCH + XCH) / NW;
-  constexpr int STAGE = (WCH + XCH) * 1024;
+  constexpr int RP = 128, NI = 2, TQ = RP / 32, KP = NKT * 32;
   constexpr int IMG = (RP + 2 * KP) * 128;                // Q | K | V images of one head
-  static_assert((WCH + XCH) % NW == 0, "every wave stages the same number of pieces");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ovqa::AttnArgs& a = g.att;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wc = wave / (2 * NH), wr = wave % (2 * NH);  // 4 row quarters x 2 NH feature slabs of 32
   const int h0 = blockIdx.y * NH, b = blockIdx.x, nq = a.nq, nk = a.nk;
 
-  f32x4 acc[NJ][NI];
-#pragma unroll
-  for (int j = 0; j < NJ; j++)
-#pragma unroll
-    for (int i = 0; i < NI; i++) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto off32 = [&](int row, int ch) { return row * (BKF * 2) + ((ch ^ (row & 7)) << 4); };
-  const bf16* src[PER];
-#pragma unroll
-  for (int i = 0; i < PER; i++) {
-    const int ci = wave + NW * i;
-    const int prow = lane / CHR, pch = lane % CHR;
-    if (ci < WCH) {  // the heads' fc_q rows, permuted within 32 (a lane then owns 8 consecutive output features)
-      const int row = ci * PROWS + prow;
-      src[i] = g.w + (int64_t)(h0 * 64 + perm32(row)) * g.Dm + ((pch ^ (row & 7)) << 3);
-    } else {         // x rows of the sample, clamped to its last row
-      const int row = (ci - WCH) * PROWS + prow;
-      const int r = row < nq ? row : nq - 1;
-      src[i] = g.x + ((int64_t)b * nq + r) * g.ldx + ((pch ^ (row & 7)) << 3);
-    }
-  }
+  f32x4 acc[2][NI];
+  QProj<NBUF, NH> pl;
+  // the heads' fc_q rows, permuted within 32 (a lane then owns 8 consecutive output features); x rows of the sample,
+  // clamped to its last row
+  pl.setup(acc, wave, lane, [&](int row) { return g.w + (int64_t)(h0 * 64 + perm32(row)) * g.Dm; },
+           [&](int row) { return g.x + ((int64_t)b * nq + (row < nq ? row : nq - 1)) * g.ldx; });
   float4 bias_r[2];
   {
     const int f = h0 * 64 + wr * 32 + (lane >> 4) * 8;
     bias_r[0] = g.bias ? *reinterpret_cast<const float4*>(g.bias + f) : make_float4(0.f, 0.f, 0.f, 0.f);
     bias_r[1] = g.bias ? *reinterpret_cast<const float4*>(g.bias + f + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  auto issue = [&](int kt) {
-    char* buf = smem + (kt % NBUF) * STAGE;
-#pragma unroll
-    for (int i = 0; i < PER; i++)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src[i] + kt * BKF), (lds_void*)(buf + (wave + NW * i) * 1024), 16, 0, 0);
-  };
-  const int nkt = g.Dm / BKF;
-#pragma unroll
-  for (int p = 0; p < NBUF - 1; p++)
-    if (p < nkt) issue(p);
-  for (int kt = 0; kt < nkt; kt++) {
-    if (kt + NBUF - 2 >= nkt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NBUF - 2)) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (kt + NBUF - 1 < nkt) issue(kt + NBUF - 1);
-    const char* Ws = smem + (kt % NBUF) * STAGE;
-    const char* Xs = Ws + WCH * 1024;
-#pragma unroll
-    for (int ks = 0; ks < BKF / 32; ks++) {
-      bf16x8 pf[NJ], qf[NI];
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-        pf[j] = *reinterpret_cast<const bf16x8*>(Ws + off32(wr * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int i = 0; i < NI; i++)
-        qf[i] = *reinterpret_cast<const bf16x8*>(Xs + off32(wc * 32 + i * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-#pragma unroll
-        for (int i = 0; i < NI; i++) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[j], qf[i], acc[j][i], 0, 0, 0);
-    }
-  }
+  pl.run(acc, smem, wave, lane, wr, wc, g.Dm / 64);
   __syncthreads();  // every wave is done with the staging buffers: they become the Q | K | V images
 
   // ---- images per head: Q [RP][64] from the accumulators (+ bias; also to HBM), K | V [KP][64] from HBM; mask rows behind
@@ -582,11 +471,7 @@ __global__ __launch_bounds__(512 * NH) void attn_q_fwd_mfma_kernel(QAttnArgs g) 
     for (int i = 0; i < NI; i++) {
       const int r = wc * 32 + i * 16 + (lane & 15);
       const int col = (wr & 1) * 32 + (lane >> 4) * 8;
-      bf16x8 o8;
-      o8[0] = (bf16)(acc[0][i][0] + bias_r[0].x); o8[1] = (bf16)(acc[0][i][1] + bias_r[0].y);
-      o8[2] = (bf16)(acc[0][i][2] + bias_r[0].z); o8[3] = (bf16)(acc[0][i][3] + bias_r[0].w);
-      o8[4] = (bf16)(acc[1][i][0] + bias_r[1].x); o8[5] = (bf16)(acc[1][i][1] + bias_r[1].y);
-      o8[6] = (bf16)(acc[1][i][2] + bias_r[1].z); o8[7] = (bf16)(acc[1][i][3] + bias_r[1].w);
+      const bf16x8 o8 = pack_bias8(acc[0][i], acc[1][i], bias_r[0], bias_r[1]);
       *reinterpret_cast<bf16x8*>(Qs + Img<64>::off(r, col >> 3)) = o8;
       if (r < nq) *reinterpret_cast<bf16x8*>(g.q + ((int64_t)b * nq + r) * g.ldq + (h0 + hh) * 64 + col) = o8;
     }
@@ -1241,8 +1126,8 @@ __global__ __launch_bounds__(W == 1 ? 128 * G : 256) void attn_bwd_smallk_mfma_k
 // ------------------------------------------------ merged backward with the dO projection inside (round 3)
 // Guided attention backward (65-128 queries x <= 32 keys): dO of the head is NOT read from HBM -- it is computed here
 // from the gradient of the block's pre-LayerNorm sum, dO_h = dY W_o[:, head]  (the fc_o dX product restricted to the
-// head's 64 features: dY [128 rows, d_model] against 64 rows of the transposed weight shadow), with the projection loop
-// of attn_q_fwd_mfma_kernel; rounded to bf16 into the dO image, as the separate GEMM would have stored it.  Then Q, K, V,
+// head's 64 features: dY [128 rows, d_model] against 64 rows of the transposed weight shadow), with the shared
+// projection loop (DoProj); rounded to bf16 into the dO image, as the separate GEMM would have stored it.  Then Q, K, V,
 // the mask row and log-sum-exp are staged, delta = dO . (O + o_lo) is taken from the image and the O rows, and
 // smallk_bwd_compute runs on waves 0-3.  One launch instead of a 6400 x 512 <- 512 GEMM + the backward kernel; dO never
 // travels through HBM.
@@ -1252,88 +1137,37 @@ struct DoBwdArgs {
   ovqa::AttnBwdArgs att;            // q, k, v, o, o_lo, lse, mask, dq, dk, dv, delta, sizes (d_o unused)
   int Dm;
 };
+// 64 weight rows of one head x 128 dY rows, 8 waves (this kernel and the fused role-split one) / 128 weight rows of two
+// heads x 32 dY rows, 4 waves (attn_bwd_do_smallk1_mfma_kernel); K steps of 64
+template <int NBUF> using DoProj = ProjLoop<2, 2, 64, NBUF, 8, 64, 128>;
+template <int NBUF> using DoProj1 = ProjLoop<2, 2, 64, NBUF, 4, 128, 32>;
 
-// NH = heads per workgroup (1: 8 waves, two workgroups per CU; 2: 16 waves, dY staged once for both heads, one workgroup
-// per CU and 64 samples x 4 head pairs = one workgroup on every CU).
+// NH = heads per workgroup: built for 1 only (8 waves, two workgroups per CU).  The two-head form (16 waves, dY staged once
+// for both heads, one workgroup per CU and 64 samples x 4 head pairs = one workgroup on every CU) measured slower, see
+// mfma_attention_bwd_do, and its staging code is gone.
 template <int NBUF, int NH>
-__global__ __launch_bounds__(512 * NH, NH == 1 ? 4 : 4) void attn_bwd_do_smallk_mfma_kernel(DoBwdArgs g) {
-  constexpr int RP = 128, BKF = 64, NI = 2, NJ = 2, W = 4, NW = 8 * NH;
-  constexpr int PROWS = 8, CHR = 8, WCH = 64 * NH / PROWS, XCH = RP / PROWS, PER = (WCH + XCH) / NW;
-  constexpr int STAGE = (WCH + XCH) * 1024;
-  constexpr int q_rows = 32 * W, k_rows = 32;
-  constexpr int img_bytes = (2 * q_rows + 2 * k_rows) * 128;
-  constexpr int prob_bytes = img_bytes + k_rows * 4 + 2 * q_rows * 4 + 4096 * 4;  // (smallk_bwd_compute's layout)
-  static_assert((WCH + XCH) % NW == 0, "every wave stages the same number of pieces");
+__global__ __launch_bounds__(512, 4) void attn_bwd_do_smallk_mfma_kernel(DoBwdArgs g) {
+  static_assert(NH == 1, "one head per workgroup");
+  constexpr int W = 4, q_rows = 32 * W, k_rows = 32;
+  constexpr int img_bytes = (2 * q_rows + 2 * k_rows) * 128;  // (smallk_bwd_compute's layout)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ovqa::AttnBwdArgs& a = g.att;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wc = wave / (2 * NH), wr = wave % (2 * NH);
-  const int h0 = blockIdx.y * NH, b = blockIdx.x, nq = a.nq, nk = a.nk;
+  const int wc = wave >> 1, wr = wave & 1;
+  const int h = blockIdx.y, b = blockIdx.x, nq = a.nq, nk = a.nk;
 
-  f32x4 acc[NJ][NI];
-#pragma unroll
-  for (int j = 0; j < NJ; j++)
-#pragma unroll
-    for (int i = 0; i < NI; i++) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto off32 = [&](int row, int ch) { return row * (BKF * 2) + ((ch ^ (row & 7)) << 4); };
-  const bf16* src[PER];
-#pragma unroll
-  for (int i = 0; i < PER; i++) {
-    const int ci = wave + NW * i;
-    const int prow = lane / CHR, pch = lane % CHR;
-    if (ci < WCH) {
-      const int row = ci * PROWS + prow;
-      src[i] = g.wt + (int64_t)(h0 * 64 + perm32(row)) * g.ldwt + ((pch ^ (row & 7)) << 3);
-    } else {
-      const int row = (ci - WCH) * PROWS + prow;
-      const int r = row < nq ? row : nq - 1;
-      src[i] = g.dy + ((int64_t)b * nq + r) * g.lddy + ((pch ^ (row & 7)) << 3);
-    }
-  }
-  auto issue = [&](int kt) {
-    char* buf = smem + (kt % NBUF) * STAGE;
-#pragma unroll
-    for (int i = 0; i < PER; i++)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src[i] + kt * BKF), (lds_void*)(buf + (wave + NW * i) * 1024), 16, 0, 0);
-  };
-  const int nkt = g.Dm / BKF;
-#pragma unroll
-  for (int p = 0; p < NBUF - 1; p++)
-    if (p < nkt) issue(p);
-  for (int kt = 0; kt < nkt; kt++) {
-    if (kt + NBUF - 2 >= nkt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NBUF - 2)) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (kt + NBUF - 1 < nkt) issue(kt + NBUF - 1);
-    const char* Ws = smem + (kt % NBUF) * STAGE;
-    const char* Xs = Ws + WCH * 1024;
-#pragma unroll
-    for (int ks = 0; ks < BKF / 32; ks++) {
-      bf16x8 pf[NJ], qf[NI];
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-        pf[j] = *reinterpret_cast<const bf16x8*>(Ws + off32(wr * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int i = 0; i < NI; i++)
-        qf[i] = *reinterpret_cast<const bf16x8*>(Xs + off32(wc * 32 + i * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-#pragma unroll
-        for (int i = 0; i < NI; i++) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[j], qf[i], acc[j][i], 0, 0, 0);
-    }
-  }
+  f32x4 acc[2][2];
+  DoProj<NBUF> pl;
+  pl.setup(acc, wave, lane, [&](int row) { return g.wt + (int64_t)(h * 64 + perm32(row)) * g.ldwt; },
+           [&](int row) { return g.dy + ((int64_t)b * nq + (row < nq ? row : nq - 1)) * g.lddy; });
+  pl.run(acc, smem, wave, lane, wr, wc, g.Dm / 64);
   // (round 5 measured the requests IN FRONT of the projection loop, as attn_bwd_do_smallk1_mfma_kernel has them: 18.4 -> 19.4 us
   // per launch in the step -- nine register loads per thread of two co-resident workgroups queue ahead of the ring's first
   // tiles on the same fetch path; the role-split form showed the same)
-  // ---- everything else the backward needs is requested now (one round of loads, as in the plain kernel); per head 512
-  // threads: the first 256 take Q (4 chunks) and K, the other 256 O / o_lo (4 chunks each), V, lse; the mask row by 32
-  const int hs = tid >> 9, t5 = tid & 511;   // staging head and thread within its 512
-  const int hst = h0 + hs;
-  const int t = t5 & 255, ch = t & 7;
-  const bool ld_q = __builtin_amdgcn_readfirstlane((int)(t5 < 256)) != 0;  // (whole waves)
+  // ---- everything else the backward needs is requested now (one round of loads, as in the plain kernel): the first
+  // 256 threads take Q (4 chunks) and K, the other 256 O / o_lo (4 chunks each), V, lse; the mask row by 32
+  const int t = tid & 255, ch = t & 7;
+  const bool ld_q = __builtin_amdgcn_readfirstlane((int)(tid < 256)) != 0;  // (whole waves)
   const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
   // Every load is UNCONDITIONAL per lane (clamped row; a missing mask row / o_lo is read from another valid address and
   // dropped below) and nothing is computed from a loaded value before all are issued -- see attn_bwd_roles_mfma_kernel:
@@ -1341,15 +1175,15 @@ __global__ __launch_bounds__(512 * NH, NH == 1 ? 4 : 4) void attn_bwd_do_smallk_
   const bool has_mask = a.mask != nullptr, has_lo = a.o_lo != nullptr;
   uint4 va[W], vb[W], vkv;
   float lse_r[W];
-  const float* lb = a.lse + ((int64_t)b * a.H + hst) * nq;
-  const float* mp = has_mask ? a.mask + (int64_t)b * a.msb + (int64_t)hst * a.msh : lb;
-  float mval = mp[min(t5 & (k_rows - 1), (has_mask ? nk : nq) - 1)];
+  const float* lb = a.lse + ((int64_t)b * a.H + h) * nq;
+  const float* mp = has_mask ? a.mask + (int64_t)b * a.msb + (int64_t)h * a.msh : lb;
+  float mval = mp[min(tid & (k_rows - 1), (has_mask ? nk : nq) - 1)];
   {
-    const bf16* pa = ld_q ? (const bf16*)a.q + (int64_t)b * nq * a.ldq + hst * 64 + ch * 8
-                          : (const bf16*)a.o + (int64_t)b * nq * a.ldo + hst * 64 + ch * 8;
+    const bf16* pa = ld_q ? (const bf16*)a.q + (int64_t)b * nq * a.ldq + h * 64 + ch * 8
+                          : (const bf16*)a.o + (int64_t)b * nq * a.ldo + h * 64 + ch * 8;
     const int64_t lda = ld_q ? a.ldq : a.ldo;
     const bool lo = !ld_q && has_lo;
-    const bf16* pb = lo ? (const bf16*)a.o_lo + (int64_t)b * nq * a.ldo + hst * 64 + ch * 8 : pa;
+    const bf16* pb = lo ? (const bf16*)a.o_lo + (int64_t)b * nq * a.ldo + h * 64 + ch * 8 : pa;
 #pragma unroll
     for (int i = 0; i < W; i++) {
       const int rc = min((t >> 3) + 32 * i, nq - 1);
@@ -1359,39 +1193,23 @@ __global__ __launch_bounds__(512 * NH, NH == 1 ? 4 : 4) void attn_bwd_do_smallk_
     }
     const int kc = min(t >> 3, nk - 1);
     const bf16* pk = ld_q ? (const bf16*)a.k + ((int64_t)b * nk + kc) * a.ldk : (const bf16*)a.v + ((int64_t)b * nk + kc) * a.ldv;
-    vkv = *reinterpret_cast<const uint4*>(pk + hst * 64 + ch * 8);
+    vkv = *reinterpret_cast<const uint4*>(pk + h * 64 + ch * 8);
   }
   __syncthreads();  // every wave is done with the staging ring: it becomes the images
 
-  // ---- dO image [128][64] (bf16) of the wave's head from the accumulators; rows beyond nq are zero (p = 0 there anyway)
+  store_do_image(smem + q_rows * 128, acc, wc * 32, wr * 32, nq, lane);  // dO image [128][64]
+  __syncthreads();  // the dO image is complete: delta reads it
   {
-    char* Gs = smem + (wr >> 1) * prob_bytes + q_rows * 128;
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-      const int r = wc * 32 + i * 16 + (lane & 15);
-      const int col = (wr & 1) * 32 + (lane >> 4) * 8;
-      bf16x8 o8;
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        o8[e] = r < nq ? (bf16)acc[0][i][e] : (bf16)0.f;
-        o8[4 + e] = r < nq ? (bf16)acc[1][i][e] : (bf16)0.f;
-      }
-      *reinterpret_cast<bf16x8*>(Gs + img_off(r, col >> 3)) = o8;
-    }
-  }
-  __syncthreads();  // the dO images are complete: delta reads them
-  {
-    char* base = smem + hs * prob_bytes;
-    const char* Gs = base + q_rows * 128;
-    float* lse_g = reinterpret_cast<float*>(base + img_bytes) + k_rows;
-    const int pid = b * a.H + hst;
+    const char* Gs = smem + q_rows * 128;
+    float* lse_g = reinterpret_cast<float*>(smem + img_bytes) + k_rows;
+    const int pid = b * a.H + h;
 #pragma unroll
     for (int i = 0; i < W; i++) {
       const int row = (t >> 3) + 32 * i;
       const bool v = row < nq;
       if (ld_q) {
         if (!v) va[i] = zero4;
-        *reinterpret_cast<uint4*>(base + img_off(row, ch)) = va[i];
+        *reinterpret_cast<uint4*>(smem + img_off(row, ch)) = va[i];
       } else {
         if (!has_lo) vb[i] = zero4;
         const bf16x8 g8 = *reinterpret_cast<const bf16x8*>(Gs + img_off(row, ch));  // (zero beyond nq: dl = 0 there)
@@ -1412,15 +1230,13 @@ __global__ __launch_bounds__(512 * NH, NH == 1 ? 4 : 4) void attn_bwd_do_smallk_
     }
     const int krow = t >> 3;
     if (krow >= nk) vkv = zero4;
-    if (ld_q) *reinterpret_cast<uint4*>(base + 2 * q_rows * 128 + img_off(krow, ch)) = vkv;
-    else *reinterpret_cast<uint4*>(base + (2 * q_rows + k_rows) * 128 + img_off(krow, ch)) = vkv;
-    if (t5 < k_rows) reinterpret_cast<float*>(base + img_bytes)[t5] = t5 < nk ? (has_mask ? mval * LOG2E : 0.f) : -INFINITY;
+    if (ld_q) *reinterpret_cast<uint4*>(smem + 2 * q_rows * 128 + img_off(krow, ch)) = vkv;
+    else *reinterpret_cast<uint4*>(smem + (2 * q_rows + k_rows) * 128 + img_off(krow, ch)) = vkv;
+    if (tid < k_rows) reinterpret_cast<float*>(smem + img_bytes)[tid] = tid < nk ? (has_mask ? mval * LOG2E : 0.f) : -INFINITY;
   }
   __syncthreads();
-  // waves 0 .. 4 NH - 1: head wave / 4, query tile wave % 4; the others keep the barriers company
-  const int hc = wave >> 2;
-  smallk_bwd_compute<true, W, 1>(a, smem + (hc < NH ? hc : 0) * prob_bytes, b * a.H + h0 + (hc < NH ? hc : 0), wave & 3, lane,
-                                 hc >= NH);
+  // waves 0-3: one query tile each; the others keep the barriers company
+  smallk_bwd_compute<true, W, 1>(a, smem, b * a.H + h, wave & 3, lane, wave >= 4);
 }
 
 // The same for <= 32 queries x <= 32 keys (the question self-attention, 20 x 20): a 4-wave workgroup takes TWO heads of a
@@ -1428,13 +1244,9 @@ __global__ __launch_bounds__(512 * NH, NH == 1 ? 4 : 4) void attn_bwd_do_smallk_
 // and runs the single-tile merged backward (waves 0-1: dQ of the two heads, waves 2-3: dK / dV).
 template <int NBUF>
 __global__ __launch_bounds__(256) void attn_bwd_do_smallk1_mfma_kernel(DoBwdArgs g) {
-  constexpr int BKF = 64, NI = 2, NJ = 2, G = 2, NW = 4;
-  constexpr int PROWS = 8, CHR = 8, WCH = 128 / PROWS, XCH = 32 / PROWS, PER = (WCH + XCH) / NW;
-  constexpr int STAGE = (WCH + XCH) * 1024;
-  constexpr int q_rows = 32, k_rows = 32;
+  constexpr int G = 2, q_rows = 32, k_rows = 32;
   constexpr int img_bytes = (2 * q_rows + 2 * k_rows) * 128;
   constexpr int prob_bytes = img_bytes + k_rows * 4 + 2 * q_rows * 4 + 4096 * 4;  // (smallk_bwd_compute's layout)
-  static_assert((WCH + XCH) % NW == 0, "every wave stages the same number of pieces");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ovqa::AttnBwdArgs& a = g.att;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1442,32 +1254,10 @@ __global__ __launch_bounds__(256) void attn_bwd_do_smallk1_mfma_kernel(DoBwdArgs
   const int h0 = blockIdx.y * G, b = blockIdx.x, nq = a.nq, nk = a.nk;
 
   OVQA_PROBE(0);
-  f32x4 acc[NJ][NI];
-#pragma unroll
-  for (int j = 0; j < NJ; j++)
-#pragma unroll
-    for (int i = 0; i < NI; i++) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto off32 = [&](int row, int ch) { return row * (BKF * 2) + ((ch ^ (row & 7)) << 4); };
-  const bf16* src[PER];
-#pragma unroll
-  for (int i = 0; i < PER; i++) {
-    const int ci = wave + NW * i;
-    const int prow = lane / CHR, pch = lane % CHR;
-    if (ci < WCH) {
-      const int row = ci * PROWS + prow;
-      src[i] = g.wt + (int64_t)(h0 * 64 + perm32(row)) * g.ldwt + ((pch ^ (row & 7)) << 3);
-    } else {
-      const int row = (ci - WCH) * PROWS + prow;
-      const int r = row < nq ? row : nq - 1;
-      src[i] = g.dy + ((int64_t)b * nq + r) * g.lddy + ((pch ^ (row & 7)) << 3);
-    }
-  }
-  auto issue = [&](int kt) {
-    char* buf = smem + (kt % NBUF) * STAGE;
-#pragma unroll
-    for (int i = 0; i < PER; i++)
-      __builtin_amdgcn_global_load_lds((gbl_void*)(src[i] + kt * BKF), (lds_void*)(buf + (wave + NW * i) * 1024), 16, 0, 0);
-  };
+  f32x4 acc[2][2];
+  DoProj1<NBUF> pl;
+  pl.setup(acc, wave, lane, [&](int row) { return g.wt + (int64_t)(h0 * 64 + perm32(row)) * g.ldwt; },
+           [&](int row) { return g.dy + ((int64_t)b * nq + (row < nq ? row : nq - 1)) * g.lddy; });
   // ---- one round of loads for both heads: every thread owns chunk (row tid >> 3, 16 bytes tid & 7) of every image
   const int ch = tid & 7, row = tid >> 3;
   const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
@@ -1492,55 +1282,13 @@ __global__ __launch_bounds__(256) void attn_bwd_do_smallk1_mfma_kernel(DoBwdArgs
   }
   // (requested BEFORE the projection loop, round 5: Q, K, V, O arrive under it instead of in a round trip of their own
   // behind it -- 1.1 us per workgroup by the phase probe, 3.1 from cold caches)
-  const int nkt = g.Dm / BKF;
-#pragma unroll
-  for (int p = 0; p < NBUF - 1; p++)
-    if (p < nkt) issue(p);
-  for (int kt = 0; kt < nkt; kt++) {
-    if (kt + NBUF - 2 >= nkt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (NBUF - 2)) : "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (kt + NBUF - 1 < nkt) issue(kt + NBUF - 1);
-    const char* Ws = smem + (kt % NBUF) * STAGE;
-    const char* Xs = Ws + WCH * 1024;
-#pragma unroll
-    for (int ks = 0; ks < BKF / 32; ks++) {
-      bf16x8 pf[NJ], qf[NI];
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-        pf[j] = *reinterpret_cast<const bf16x8*>(Ws + off32(wr * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int i = 0; i < NI; i++)
-        qf[i] = *reinterpret_cast<const bf16x8*>(Xs + off32(i * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-      for (int j = 0; j < NJ; j++)
-#pragma unroll
-        for (int i = 0; i < NI; i++) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[j], qf[i], acc[j][i], 0, 0, 0);
-    }
-  }
+  pl.run(acc, smem, wave, lane, wr, 0, g.Dm / 64);
   OVQA_PROBE(1);
   OVQA_PROBE(2);
   __syncthreads();  // every wave is done with the staging ring: it becomes the images
 
-  // ---- dO image [32][64] (bf16) of the wave's head from the accumulators; rows beyond nq are zero
-  {
-    char* Gs = smem + (wr >> 1) * prob_bytes + q_rows * 128;
-#pragma unroll
-    for (int i = 0; i < NI; i++) {
-      const int r = i * 16 + (lane & 15);
-      const int col = (wr & 1) * 32 + (lane >> 4) * 8;
-      bf16x8 o8;
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        o8[e] = r < nq ? (bf16)acc[0][i][e] : (bf16)0.f;
-        o8[4 + e] = r < nq ? (bf16)acc[1][i][e] : (bf16)0.f;
-      }
-      *reinterpret_cast<bf16x8*>(Gs + img_off(r, col >> 3)) = o8;
-    }
-  }
+  // ---- dO image [32][64] of the wave's head (wr >> 1), feature half wr & 1
+  store_do_image(smem + (wr >> 1) * prob_bytes + q_rows * 128, acc, 0, (wr & 1) * 32, nq, lane);
   __syncthreads();  // the dO images are complete: delta reads them
 #pragma unroll
   for (int gi = 0; gi < G; gi++) {
@@ -1588,17 +1336,18 @@ __global__ __launch_bounds__(256) void attn_bwd_do_smallk1_mfma_kernel(DoBwdArgs
 #ifndef OVQA_ROLES_WAVES_PER_EU
 #define OVQA_ROLES_WAVES_PER_EU 4
 #endif
-// FUSE_NBUF > 0 (round 5; needs NQT_T = NKT_T = 4): the fc_o dX product inside, the form attn_bwd_do_smallk_mfma_kernel
-// has for the guided attention -- dO of the head = dY [128 rows, d_model] x 64 rows of the transposed fc_o weights, with
-// that kernel's projection loop (ring of FUSE_NBUF K steps of 64: 24 KB each, aliased with the images), rounded to bf16
-// straight into the dO image; grid (B, H), so that the 8 heads of a sample -- which all stream the sample's dY rows --
-// share an XCD.  dO never travels through HBM and the 6400 x 512 <- 512 dX launch in front of this kernel is gone.
+// FUSE_NBUF = ring depth of the fused form, 0 = not fused (round 5; needs NQT_T = NKT_T = 4 and DMA): the fc_o dX product
+// inside, the form attn_bwd_do_smallk_mfma_kernel has for the guided attention -- dO of the head = dY [128 rows, d_model]
+// x 64 rows of the transposed fc_o weights, with that kernel's projection loop (DoProj: the shared ProjLoop with a ring of
+// FUSE_NBUF K steps of 64, 24 KB each, aliased with the images), rounded to bf16 straight into the dO image; grid (B, H),
+// so that the 8 heads of a sample -- which all stream the sample's dY rows -- share an XCD.  dO never travels through HBM
+// and the 6400 x 512 <- 512 dX launch in front of this kernel is gone.
 template <int NQT_T, int NKT_T, bool ROWMASK, int FUSE_NBUF = 0, bool DMA = false>
 __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1) void attn_bwd_roles_mfma_kernel(DoBwdArgs g, int nqt_rt, int nkt_rt) {
-  constexpr bool FUSE = FUSE_NBUF > 0, EARLY = FUSE_NBUF >= 10;
+  constexpr bool FUSE = FUSE_NBUF > 0;
   static_assert(!DMA || ROWMASK, "clamped rows rely on the key mask row / lse to vanish");
-  constexpr int RING = FUSE ? FUSE_NBUF % 10 : 1;  // (1: never used, keeps the un-fused instantiations free of a % 0)
   static_assert(!FUSE || (NQT_T == 4 && NKT_T == 4), "the fused form is built for 4 x 4 tiles");
+  static_assert(!FUSE || DMA, "the fused form fills its images by direct-to-LDS loads");
   const ovqa::AttnBwdArgs& a = g.att;
   const int nqt = NQT_T ? NQT_T : nqt_rt, nkt = NKT_T ? NKT_T : nkt_rt;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1620,73 +1369,19 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
   OVQA_PROBE(0);
   // ---- (fused form) dO of the head into accumulators: acc[j][i] = 16 rows (wc * 32 + i * 16 ..) x 16 features
   // (wr * 32 + j * 16 ..) per wave, the staging ring over the (not yet written) images
-  constexpr int PJ_NI = 2, PJ_NJ = 2;
-  f32x4 acc[PJ_NJ][PJ_NI];
+  f32x4 acc[2][2];
   const int wc = wave >> 1, wr = wave & 1;
-  // the projection loop of the fused form; EARLY (FUSE_NBUF >= 10): it runs BEHIND the staging requests below, so that Q, K, V,
-  // O arrive under it.  MEASURED (phase probe, round 5): slower -- the 14 register loads per thread of two co-resident
-  // workgroups take 3.4 us just to issue (8-9 from cold caches: the CU's fetch path is the bottleneck either way) and the
-  // ring's first tiles queue behind them: 19.9 against 17.6-18.8 us per workgroup warm, 27.4 against 26.4 cold.
-  auto project = [&]() {
-    constexpr int BKF = 64, NW = 8, PROWS = 8, CHR = 8, WCH = 64 / PROWS, XCH = 128 / PROWS, PER = (WCH + XCH) / NW;
-    constexpr int STAGE = (WCH + XCH) * 1024;
-#pragma unroll
-    for (int j = 0; j < PJ_NJ; j++)
-#pragma unroll
-      for (int i = 0; i < PJ_NI; i++) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto off32 = [&](int row, int ch) { return row * (BKF * 2) + ((ch ^ (row & 7)) << 4); };
-    const bf16* src[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-      const int ci = wave + NW * i;
-      const int prow = lane / CHR, pch = lane % CHR;
-      if (ci < WCH) {
-        const int row = ci * PROWS + prow;
-        src[i] = g.wt + (int64_t)(h * 64 + perm32(row)) * g.ldwt + ((pch ^ (row & 7)) << 3);
-      } else {
-        const int row = (ci - WCH) * PROWS + prow;
-        const int r = row < nq ? row : nq - 1;
-        src[i] = g.dy + ((int64_t)b * nq + r) * g.lddy + ((pch ^ (row & 7)) << 3);
-      }
-    }
-    auto issue = [&](int kt) {
-      char* buf = smem + (kt % RING) * STAGE;
-#pragma unroll
-      for (int i = 0; i < PER; i++)
-        __builtin_amdgcn_global_load_lds((gbl_void*)(src[i] + kt * BKF), (lds_void*)(buf + (wave + NW * i) * 1024), 16, 0, 0);
-    };
-    const int nkt_p = g.Dm / BKF;
-#pragma unroll
-    for (int p = 0; p < RING - 1; p++)
-      if (p < nkt_p) issue(p);
-    for (int kt = 0; kt < nkt_p; kt++) {
-      if (kt + RING - 2 >= nkt_p) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER * (RING - 2)) : "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      if (kt + RING - 1 < nkt_p) issue(kt + RING - 1);
-      const char* Ws = smem + (kt % RING) * STAGE;
-      const char* Xs = Ws + WCH * 1024;
-#pragma unroll
-      for (int ks = 0; ks < BKF / 32; ks++) {
-        bf16x8 pf[PJ_NJ], qf[PJ_NI];
-#pragma unroll
-        for (int j = 0; j < PJ_NJ; j++)
-          pf[j] = *reinterpret_cast<const bf16x8*>(Ws + off32(wr * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-        for (int i = 0; i < PJ_NI; i++)
-          qf[i] = *reinterpret_cast<const bf16x8*>(Xs + off32(wc * 32 + i * 16 + (lane & 15), ks * 4 + (lane >> 4)));
-#pragma unroll
-        for (int j = 0; j < PJ_NJ; j++)
-#pragma unroll
-          for (int i = 0; i < PJ_NI; i++) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[j], qf[i], acc[j][i], 0, 0, 0);
-      }
-    }
+  // The loop runs IN FRONT of the staging requests below.  MEASURED (phase probe, round 5) with the loop behind them, so
+  // that Q, K, V, O arrive under it: slower -- the 14 register loads per thread of two co-resident workgroups take 3.4 us
+  // just to issue (8-9 from cold caches: the CU's fetch path is the bottleneck either way) and the ring's first tiles queue
+  // behind them: 19.9 against 17.6-18.8 us per workgroup warm, 27.4 against 26.4 cold.
+  if constexpr (FUSE) {
+    DoProj<FUSE_NBUF> pl;
+    pl.setup(acc, wave, lane, [&](int row) { return g.wt + (int64_t)(h * 64 + perm32(row)) * g.ldwt; },
+             [&](int row) { return g.dy + ((int64_t)b * nq + (row < nq ? row : nq - 1)) * g.lddy; });
+    pl.run(acc, smem, wave, lane, wr, wc, g.Dm / 64);
     OVQA_PROBE(6);
-  };
-  if constexpr (FUSE && !EARLY) project();
+  }
   // ---- staging: one round of global loads (all issued before the first LDS store): a thread owns chunk `ch` of rows
   // r0 and r0 + 64 of each of Q, dO, K, V -- and of O, so that delta = dO . O falls out of the staging (8 consecutive
   // lanes hold a row) instead of a second, dependent pass over dO and O.
@@ -1739,7 +1434,7 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
       const int row = r0 + 64 * i;
       const int rq = min(row, nq - 1), rk = min(row, nk - 1);
       if constexpr (!DMA) vq[i] = *reinterpret_cast<const uint4*>(qb + (int64_t)rq * a.ldq);
-      if constexpr (!DMA && !FUSE) vd[i] = *reinterpret_cast<const uint4*>(gb + (int64_t)rq * a.lddo);
+      if constexpr (!DMA) vd[i] = *reinterpret_cast<const uint4*>(gb + (int64_t)rq * a.lddo);
       vo[i] = *reinterpret_cast<const uint4*>(ob + (int64_t)rq * a.ldo);
       vl[i] = *reinterpret_cast<const uint4*>(lob2 + (int64_t)rq * a.ldo);
       lse_r[i] = lb[rq];
@@ -1749,24 +1444,10 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
       }
     }
     OVQA_PROBE(1);
-    if constexpr (FUSE && EARLY) project();
     if constexpr (FUSE) {
       __syncthreads();  // every wave is done with the staging ring: it becomes the images
-      if constexpr (DMA) dma_qkv();
-      // dO image [128][64] (bf16) from the accumulators; rows beyond nq are zero
-#pragma unroll
-      for (int i = 0; i < PJ_NI; i++) {
-        const int r = wc * 32 + i * 16 + (lane & 15);
-        const int col = wr * 32 + (lane >> 4) * 8;
-        bf16x8 o8;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          o8[e] = r < nq ? (bf16)acc[0][i][e] : (bf16)0.f;
-          o8[4 + e] = r < nq ? (bf16)acc[1][i][e] : (bf16)0.f;
-        }
-        *reinterpret_cast<bf16x8*>(Gs + img_off(r, col >> 3)) = o8;
-      }
-      if constexpr (!DMA) __syncthreads();  // the dO image is complete: delta reads it
+      dma_qkv();
+      store_do_image(Gs, acc, wc * 32, wr * 32, nq, lane);  // dO image [128][64]
     }
     if constexpr (DMA) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1777,7 +1458,7 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
       const int row = r0 + 64 * i;
       const bool qv = row < nq, kv = row < nk;
       if (!has_lo) vl[i] = zero4;
-      if constexpr (FUSE || DMA) vd[i] = *reinterpret_cast<const uint4*>(Gs + img_off(min(row, q_rows - 1), ch));
+      if constexpr (DMA) vd[i] = *reinterpret_cast<const uint4*>(Gs + img_off(min(row, q_rows - 1), ch));
       const bf16x8 g8 = *reinterpret_cast<const bf16x8*>(&vd[i]);
       const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(&vo[i]);
       const bf16x8 l8 = *reinterpret_cast<const bf16x8*>(&vl[i]);
@@ -1792,8 +1473,10 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
         if (!kv) { vk[i] = zero4; vv[i] = zero4; }
       }
       if (row < q_rows) {
-        if constexpr (!DMA) *reinterpret_cast<uint4*>(Qs + img_off(row, ch)) = vq[i];
-        if constexpr (!DMA && !FUSE) *reinterpret_cast<uint4*>(Gs + img_off(row, ch)) = vd[i];
+        if constexpr (!DMA) {
+          *reinterpret_cast<uint4*>(Qs + img_off(row, ch)) = vq[i];
+          *reinterpret_cast<uint4*>(Gs + img_off(row, ch)) = vd[i];
+        }
         if (ch == 0) {
           lse_s[row] = qv ? lse_r[i] * LOG2E : INFINITY;
           del_s[row] = qv ? dl : 0.f;
@@ -2170,9 +1853,8 @@ int mfma_attention_qkv_fwd(const AttnArgs& a, const void* x, int64_t ldx, const 
   // the key mask row (zeros when there is no mask, -inf beyond n) always lives in LDS: ROWMASK = true
 #define OVQA_QKV(RPV, SV, BKV, NBV)                                                                                \
   {                                                                                                                \
-    constexpr int Mv = RPV * SV;                                                                                   \
-    const size_t stage = (size_t)(192 + Mv) * BKV * 2, images = (size_t)SV * 3 * RPV * 128 + (size_t)SV * RPV * 4; \
-    const size_t lds = NBV * stage > images ? NBV * stage : images;                                                \
+    const size_t images = (size_t)SV * 3 * RPV * 128 + (size_t)SV * RPV * 4;                                       \
+    const size_t lds = std::max<size_t>(QkvProj<RPV, SV, BKV, NBV>::RING_BYTES, images);                           \
     const dim3 grid((unsigned)((a.B + SV - 1) / SV), (unsigned)a.H);                                               \
     int rc = ensure_lds(attn_qkv_fwd_mfma_kernel<RPV, SV, true, BKV, NBV>, lds, "attention_qkv_fwd");              \
     if (rc != OVQA_OK) return rc;                                                                                  \
@@ -2216,9 +1898,8 @@ int mfma_attention_q_fwd(const AttnArgs& a, const void* x, int64_t ldx, const vo
   const dim3 grid((unsigned)a.B, (unsigned)(a.H / NHv));
 #define OVQA_QATT_L(NKTV, NBV, NHV)                                                                            \
   {                                                                                                            \
-    const size_t stage = (size_t)(64 * NHV + 128) * 64 * 2;                                                    \
     const size_t images = (size_t)NHV * ((128 + 2 * NKTV * 32) * 128 + NKTV * 32 * 4);                         \
-    const size_t lds = NBV * stage > images ? NBV * stage : images;                                            \
+    const size_t lds = std::max<size_t>(QProj<NBV, NHV>::RING_BYTES, images);                                  \
     int rc = ensure_lds(attn_q_fwd_mfma_kernel<NKTV, NBV, NHV>, lds, "attention_q_fwd");                       \
     if (rc != OVQA_OK) return rc;                                                                              \
     OVQA_LAUNCH_TIMED((attn_q_fwd_mfma_kernel<NKTV, NBV, NHV>), grid, dim3(512 * NHV), lds, st, g);           \
@@ -2254,21 +1935,19 @@ int mfma_attention_bwd_do(const AttnBwdArgs& a, const void* dy, int64_t lddy, co
   DoBwdArgs g{(const bf16*)dy, lddy, (const bf16*)wt, ldwt, a, (int)Dm};
   if (a.nk > 32) {  // the role-split form (image self-attention)
     const size_t img = (size_t)(2 * 128 + 2 * 128) * 128 + (size_t)(128 + 2 * 128) * 4;
-    const size_t stage = (size_t)(64 + 128) * 64 * 2;
     // ring of three K steps in the projection loop, images filled by direct-to-LDS loads (round 5, same box: 25.6 us per
     // launch; ring of 2: 28.7; staging requests in front of the projection loop: 27.8; images through registers: 26.1)
-    const size_t lds = 3 * stage > img ? 3 * stage : img;
+    const size_t lds = std::max<size_t>(DoProj<3>::RING_BYTES, img);
     int rc = ensure_lds(attn_bwd_roles_mfma_kernel<4, 4, true, 3, true>, lds, "attention_bwd_do(roles)");
     if (rc != OVQA_OK) return rc;
     OVQA_LAUNCH_TIMED((attn_bwd_roles_mfma_kernel<4, 4, true, 3, true>), dim3((unsigned)a.B, (unsigned)a.H), dim3(512), lds, st, g, 4, 4);
     return ovqa_check_launch("attention_bwd_do(mfma,roles)");
   }
   if (a.nq <= 32) {  // single query tile (20 x 20): two heads per 4-wave workgroup
-    const size_t stage1 = (size_t)(128 + 32) * 64 * 2;
     const size_t prob1 = (size_t)(2 * 32 + 2 * 32) * 128 + 32 * 4 + 2 * 32 * 4 + 4096 * 4;
     // ring of four K steps of 20 KB in the projection loop (in the MCAN step 9.9 us per launch against 10.35-10.54 with
     // three, 10.6 with five: round 5)
-    const size_t ldsn = 4 * stage1 > 2 * prob1 ? 4 * stage1 : 2 * prob1;
+    const size_t ldsn = std::max<size_t>(DoProj1<4>::RING_BYTES, 2 * prob1);
     int rc = ensure_lds(attn_bwd_do_smallk1_mfma_kernel<4>, ldsn, "attention_bwd_do");
     if (rc != OVQA_OK) return rc;
     OVQA_LAUNCH_TIMED((attn_bwd_do_smallk1_mfma_kernel<4>), dim3((unsigned)a.B, (unsigned)(a.H / 2)), dim3(256), ldsn, st, g);
@@ -2276,14 +1955,11 @@ int mfma_attention_bwd_do(const AttnBwdArgs& a, const void* dy, int64_t lddy, co
   }
   const size_t prob = (size_t)(2 * 128 + 2 * 32) * 128 + 32 * 4 + 2 * 128 * 4 + 4096 * 4;
   // one head per 8-wave workgroup, two workgroups per CU (two heads per 16-wave workgroup: 3.265 / 3.256 against
-  // 3.241 / 3.239 ms per MCAN step since the staging became one round of loads)
-  {
-    const size_t stage = (size_t)(64 + 128) * 64 * 2;
-    const size_t lds = 3 * stage > prob ? 3 * stage : prob;
-    int rc = ensure_lds(attn_bwd_do_smallk_mfma_kernel<3, 1>, lds, "attention_bwd_do");
-    if (rc != OVQA_OK) return rc;
-    OVQA_LAUNCH_TIMED((attn_bwd_do_smallk_mfma_kernel<3, 1>), dim3((unsigned)a.B, (unsigned)a.H), dim3(512), lds, st, g);
-  }
+  // 3.241 / 3.239 ms per MCAN step since the staging became one round of loads; that form is no longer built)
+  const size_t lds = std::max<size_t>(DoProj<3>::RING_BYTES, prob);
+  int rc = ensure_lds(attn_bwd_do_smallk_mfma_kernel<3, 1>, lds, "attention_bwd_do");
+  if (rc != OVQA_OK) return rc;
+  OVQA_LAUNCH_TIMED((attn_bwd_do_smallk_mfma_kernel<3, 1>), dim3((unsigned)a.B, (unsigned)a.H), dim3(512), lds, st, g);
   return ovqa_check_launch("attention_bwd_do(mfma)");
 }
 
