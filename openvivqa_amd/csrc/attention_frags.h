@@ -1,6 +1,7 @@
 // Fragment helpers shared by the LDS-resident (attention_mfma.hip) and streaming (attention_stream.hip) MFMA attention
 // kernels: the swizzled [rows][D] bf16 image, the 32x32x16 operand fragments read from it, the accumulator row order,
 // the packed hi / lo probability and the 4-element dropout multipliers.
+// (What the backward kernels of both files share on top of these: attention_bwd_tile.h.)
 #pragma once
 #include "common.h"
 

@@ -38,6 +38,7 @@ extern "C" int ovqa_debug_probe(unsigned long long* out) {
 #endif
 
 #include "attention_frags.h"
+#include "attention_bwd_tile.h"
 #include "attention_project.h"
 
 namespace {
@@ -636,18 +637,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(ovqa::AttnBwdArgs
         dqt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(Ks, t * 32 + 16 * s, d * 32, lane), db, dqt[d], 0, 0, 0);
     }
   }
-  if (qok) {
-    bf16* drow = (bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * D;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; g4++) {
-        bf16x4 o4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) o4[e] = (bf16)(dqt[d][4 * g4 + e] * a.scale);
-        *reinterpret_cast<bf16x4*>(drow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = o4;
-      }
-  }
+  if (qok) store_acc_rows<D>((bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * D, dqt, a.scale, lane);
 }
 
 // Kernel B: one wave = 32 keys (columns).  For every query tile (rows):
@@ -765,23 +755,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_mfma_kernel(ovqa::AttnBwdArg
       }
     }
   }
-  if (kok) {
-    bf16* dkrow = (bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * D;
-    bf16* dvrow = (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * D;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; g4++) {
-        bf16x4 k4, v4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          k4[e] = (bf16)(dkt[d][4 * g4 + e] * a.scale);
-          v4[e] = (bf16)dvt[d][4 * g4 + e];
-        }
-        *reinterpret_cast<bf16x4*>(dkrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = k4;
-        *reinterpret_cast<bf16x4*>(dvrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = v4;
-      }
-  }
+  if (kok)
+    store_acc_rows<D>((bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * D, dkt, a.scale,
+                      (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * D, dvt, lane);
 }
 
 
@@ -884,18 +860,7 @@ __device__ __forceinline__ void smallk_bwd_compute(const ovqa::AttnBwdArgs& a, c
         for (int d = 0; d < 2; d++)
           dqt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Ks, 16 * s2, d * 32, lane), db, dqt[d], 0, 0, 0);
       }
-      if (qok) {
-        bf16* drow = (bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * 64;
-#pragma unroll
-        for (int d = 0; d < 2; d++)
-#pragma unroll
-          for (int g4 = 0; g4 < 4; g4++) {
-            bf16x4 o4;
-#pragma unroll
-            for (int e = 0; e < 4; e++) o4[e] = (bf16)(dqt[d][4 * g4 + e] * a.scale);
-            *reinterpret_cast<bf16x4*>(drow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = o4;
-          }
-      }
+      if (qok) store_acc_rows<64>((bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * 64, dqt, a.scale, lane);
     }
     OVQA_PROBE(4);
     // ---- direct orientation (role 1): P and dS of this query tile, rows = queries, lane = key
@@ -955,23 +920,9 @@ __device__ __forceinline__ void smallk_bwd_compute(const ovqa::AttnBwdArgs& a, c
             dkt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Qs, 16 * s2, d * 32, lane), db[s2], dkt[d], 0, 0, 0);
           }
         OVQA_PROBE(5);
-        if (kok) {
-          bf16* dkrow = (bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * 64;
-          bf16* dvrow = (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * 64;
-#pragma unroll
-          for (int d = 0; d < 2; d++)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; g4++) {
-              bf16x4 k4, v4;
-#pragma unroll
-              for (int e = 0; e < 4; e++) {
-                v4[e] = (bf16)dvt[d][4 * g4 + e];
-                k4[e] = (bf16)(dkt[d][4 * g4 + e] * a.scale);
-              }
-              *reinterpret_cast<bf16x4*>(dkrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = k4;
-              *reinterpret_cast<bf16x4*>(dvrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = v4;
-            }
-        }
+        if (kok)
+          store_acc_rows<64>((bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * 64, dkt, a.scale,
+                             (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * 64, dvt, lane);
       }
     }
   }
@@ -999,14 +950,7 @@ __device__ __forceinline__ void smallk_bwd_compute(const ovqa::AttnBwdArgs& a, c
         }
         if (key < nk) {
           bf16* row = (is_k ? (bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk : (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv) + h * 64;
-          const float sc = is_k ? a.scale : 1.f;
-#pragma unroll
-          for (int g4 = 0; g4 < 4; g4++) {
-            bf16x4 o4;
-#pragma unroll
-            for (int e = 0; e < 4; e++) o4[e] = (bf16)(out[4 * g4 + e] * sc);
-            *reinterpret_cast<bf16x4*>(row + d * 32 + 8 * g4 + 4 * (lane >> 5)) = o4;
-          }
+          store_acc_tile(row + d * 32, out, is_k ? a.scale : 1.f, lane);
         }
       }
     }
@@ -1560,18 +1504,7 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
           dqt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Ks, t * 32 + 16 * s2, d * 32, lane), db, dqt[d], 0, 0, 0);
       }
     }
-    if (qok) {
-      bf16* drow = (bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * 64;
-#pragma unroll
-      for (int d = 0; d < 2; d++)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; g4++) {
-          bf16x4 o4;
-#pragma unroll
-          for (int e = 0; e < 4; e++) o4[e] = (bf16)(dqt[d][4 * g4 + e] * a.scale);
-          *reinterpret_cast<bf16x4*>(drow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = o4;
-        }
-    }
+    if (qok) store_acc_rows<64>((bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * 64, dqt, a.scale, lane);
     OVQA_PROBE(4);
   } else {
     // ------------------------------------------------ role B: dK / dV of key tile tk (lane = key)
@@ -1630,23 +1563,9 @@ __global__ __launch_bounds__(512, (NQT_T && NKT_T) ? OVQA_ROLES_WAVES_PER_EU : 1
           dkt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(Qs, t * 32 + 16 * s2, d * 32, lane), db[s2], dkt[d], 0, 0, 0);
         }
     }
-    if (kok) {
-      bf16* dkrow = (bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * 64;
-      bf16* dvrow = (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * 64;
-#pragma unroll
-      for (int d = 0; d < 2; d++)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; g4++) {
-          bf16x4 k4, v4;
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            k4[e] = (bf16)(dkt[d][4 * g4 + e] * a.scale);
-            v4[e] = (bf16)dvt[d][4 * g4 + e];
-          }
-          *reinterpret_cast<bf16x4*>(dkrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = k4;
-          *reinterpret_cast<bf16x4*>(dvrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = v4;
-        }
-    }
+    if (kok)
+      store_acc_rows<64>((bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * 64, dkt, a.scale,
+                         (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * 64, dvt, lane);
     OVQA_PROBE_T(5, 256);
   }
 }

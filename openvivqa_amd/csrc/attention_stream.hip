@@ -20,6 +20,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "attention_frags.h"
+#include "attention_bwd_tile.h"
 
 namespace {
 
@@ -411,18 +412,7 @@ __global__ __launch_bounds__(256) void attn_stream_bwd_dq_kernel(ovqa::AttnBwdAr
       }
     }
   });
-  if (active && qok) {
-    bf16* drow = (bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * D;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; g4++) {
-        bf16x4 o4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) o4[e] = (bf16)(dqt[d][4 * g4 + e] * a.scale);
-        *reinterpret_cast<bf16x4*>(drow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = o4;
-      }
-  }
+  if (active && qok) store_acc_rows<D>((bf16*)a.dq + ((int64_t)b * nq + q) * a.lddq + h * D, dqt, a.scale, lane);
 }
 
 // dK / dV: grid (B*H, ceil(n_k / 128)), wave w owns 32 keys (columns); per Q | dO tile (2 x 32 queries, with their lse and
@@ -526,23 +516,9 @@ __device__ __forceinline__ void stream_bwd_dkv_body(const ovqa::AttnBwdArgs& a) 
       }
     }
   });
-  if (active && kok) {
-    bf16* dkrow = (bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * D;
-    bf16* dvrow = (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * D;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; g4++) {
-        bf16x4 k4, v4;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          k4[e] = (bf16)(dkt[d][4 * g4 + e] * a.scale);
-          v4[e] = (bf16)dvt[d][4 * g4 + e];
-        }
-        *reinterpret_cast<bf16x4*>(dkrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = k4;
-        *reinterpret_cast<bf16x4*>(dvrow + d * 32 + 8 * g4 + 4 * (lane >> 5)) = v4;
-      }
-  }
+  if (active && kok)
+    store_acc_rows<D>((bf16*)a.dk_ + ((int64_t)b * nk + key) * a.lddk + h * D, dkt, a.scale,
+                      (bf16*)a.dv_ + ((int64_t)b * nk + key) * a.lddv + h * D, dvt, lane);
 }
 
 template <int D, bool ROWMASK, bool DROP>
