@@ -392,6 +392,32 @@ int ovqa_attention_decode(int dtype, const void* q, int64_t ldq, const void* k, 
                           int64_t kv_batch_stride, int64_t group, const float* mask, int64_t ldmask,
                           void* o, int64_t ldo, int64_t R, int64_t H, int64_t n, int64_t d, float scale, void* stream);
 
+/* ovqa_attention_decode with the keys split ACROSS workgroups, for small batches and long key lists (the same
+ * attentions.py:314-327 under beam_search.py:41-62; at B = 1, H = 8 the call above runs 8 workgroups on 256 CUs, each wave a
+ * chain of one memory round trip per 128 keys).  Two launches ordered by the stream alone (no counters, no flags, no
+ * atomics): attn_decode_part_kernel on a grid of (row group, head) x slices, every workgroup running its slice of the keys
+ * as the call above runs all of them and writing its (maximum, sum, unnormalised o[d]) as fp32 into `workspace`; then
+ * attn_decode_merge_kernel, one wave per (row, head), merges the slices' records with the formulas of the in-workgroup
+ * merge and stores o.  Slice plan: chunk = ceil(n / splits) rounded up to 64 keys, slices = ceil(n / chunk), slice s = keys
+ * [s * chunk, min((s + 1) * chunk, n)) -- none empty, slices <= splits (ovqa_attention_decode_split_slices; -1 for n or
+ * splits out of range).  splits in 1 .. 32, or 0 = the automatic rule (ovqa_attention_decode_auto_splits: what it picks for
+ * the shape on the current device; 1 whenever (R / G) * H >= 2 * CUs, never more than n / 64).  One slice IS
+ * ovqa_attention_decode: same launch, same bits, ovqa_last_dispatch() = "decode"; otherwise "decode-split".  Layouts,
+ * shapes and alignment as for ovqa_attention_decode; up to 4 beams of a `group` share a read (the largest divisor of the
+ * group that is at most 4: groups of 5 and 7 read per row, 8 as two waves of 4).  Masks are additive and FINITE: a slice
+ * whose keys all carry -1e5 drops out by underflow.  Results are deterministic (the order of every sum is fixed) and differ
+ * from splits = 1 in the last bits, because that order is another one.  workspace: device memory, 16-byte aligned, at least
+ * ovqa_attention_decode_split_workspace_bytes(R, H, n, d, splits) bytes (R * H * slices * (d + 2) floats; splits = 0: enough
+ * for whatever the rule picks); NULL, misaligned or too small = OVQA_ERR_BAD_ARG before anything is launched.  It is
+ * scratch: nothing in it outlives the call. */
+int64_t ovqa_attention_decode_split_slices(int64_t n, int64_t splits);
+int64_t ovqa_attention_decode_split_workspace_bytes(int64_t R, int64_t H, int64_t n, int64_t d, int64_t splits);
+int64_t ovqa_attention_decode_auto_splits(int64_t R, int64_t H, int64_t group, int64_t n, int64_t d, int dtype);
+int ovqa_attention_decode_split(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                int64_t kv_batch_stride, int64_t group, const float* mask, int64_t ldmask,
+                                void* o, int64_t ldo, int64_t R, int64_t H, int64_t n, int64_t d, float scale,
+                                int64_t splits, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The k best entries of every row of x [R, V] (fp32, row stride ldx), best first, ties by the smaller index:
  * vals fp32 [R, k], idx int64 [R, k]; 1 <= k <= 8 and k <= V.  Candidate selection of a beam-search step
  * (beam_search.py:36-39 takes them from a full sort of the cur_beam * |V| candidates). */

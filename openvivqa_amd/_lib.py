@@ -122,6 +122,11 @@ SIGNATURES = {
                              c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp],
     "ovqa_attention_decode": [c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
                               c_i64, c_i64, c_i64, c_i64, c_f32, c_vp],
+    "ovqa_attention_decode_split": [c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                    c_i64, c_i64, c_i64, c_i64, c_f32, c_i64, c_vp, c_i64, c_vp],
+    "ovqa_attention_decode_split_slices": [c_i64, c_i64],
+    "ovqa_attention_decode_split_workspace_bytes": [c_i64, c_i64, c_i64, c_i64, c_i64],
+    "ovqa_attention_decode_auto_splits": [c_i64, c_i64, c_i64, c_i64, c_i64, c_int],
     "ovqa_topk_rows": [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     "ovqa_linear_fwd_split3": [c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64,
                                c_vp],
@@ -175,7 +180,9 @@ SIGNATURES = {
 _RESTYPE = {"ovqa_last_error": C.c_char_p, "ovqa_last_dispatch": C.c_char_p, "ovqa_launch_log": C.c_char_p,
             "ovqa_launch_log_clear": None, "ovqa_workspace_bytes": C.c_int64,
             "ovqa_lstm_saved_bytes": C.c_int64, "ovqa_lstm_scratch_bytes": C.c_int64,
-            "ovqa_lstm_persistent_max_batch": C.c_int64}
+            "ovqa_lstm_persistent_max_batch": C.c_int64,
+            "ovqa_attention_decode_split_slices": C.c_int64, "ovqa_attention_decode_split_workspace_bytes": C.c_int64,
+            "ovqa_attention_decode_auto_splits": C.c_int64}
 
 _lock = threading.Lock()
 _lib = None

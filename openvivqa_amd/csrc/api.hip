@@ -588,6 +588,49 @@ int ovqa_attention_decode(int dtype, const void* q, int64_t ldq, const void* k, 
   return ovqa::attention_decode(dtype, a, as_stream(stream));
 }
 
+int64_t ovqa_attention_decode_split_slices(int64_t n, int64_t splits) {
+  return ovqa::decode_split_slices(n, splits, nullptr);
+}
+
+int64_t ovqa_attention_decode_split_workspace_bytes(int64_t R, int64_t H, int64_t n, int64_t d, int64_t splits) {
+  return ovqa::decode_split_workspace_bytes(R, H, n, d, splits);
+}
+
+int64_t ovqa_attention_decode_auto_splits(int64_t R, int64_t H, int64_t group, int64_t n, int64_t d, int dtype) {
+  return ovqa::decode_auto_splits(R, H, group, n, d, dtype);
+}
+
+int ovqa_attention_decode_split(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                int64_t kv_batch_stride, int64_t group, const float* mask, int64_t ldmask, void* o,
+                                int64_t ldo, int64_t R, int64_t H, int64_t n, int64_t d, float scale, int64_t splits,
+                                void* workspace, int64_t workspace_bytes, void* stream) {
+  OVQA_REQUIRE(splits >= 0 && splits <= 32, OVQA_ERR_BAD_ARG, "attention_decode_split: splits %lld not in 0 .. 32",
+               (long long)splits);
+  OVQA_REQUIRE(dtype_ok(dtype), OVQA_ERR_BAD_ARG, "attention_decode_split: bad dtype %d", dtype);
+  OVQA_REQUIRE(R >= 0 && H > 0 && n >= 1 && d > 0 && group >= 1, OVQA_ERR_BAD_ARG, "attention_decode_split: bad sizes");
+  OVQA_REQUIRE(n <= (1 << 30) && group <= 0x7fffffff, OVQA_ERR_UNSUPPORTED,
+               "attention_decode_split: n > 2^30 (key indices are 32-bit) or group too large");
+  if (splits == 0) splits = ovqa::decode_auto_splits(R, H, group, n, d, dtype);
+  int64_t chunk = 0;
+  const int64_t slices = ovqa::decode_split_slices(n, splits, &chunk);
+  if (R == 0 || slices == 1)  // one slice is the unsplit call: same launch, same bits
+    return ovqa_attention_decode(dtype, q, ldq, k, ldk, v, ldv, kv_batch_stride, group, mask, ldmask, o, ldo, R, H, n, d,
+                                 scale, stream);
+  OVQA_REQUIRE(q && k && v && o, OVQA_ERR_BAD_ARG, "attention_decode_split: null pointer");
+  OVQA_REQUIRE(ldq >= H * d && ldk >= H * d && ldv >= H * d && ldo >= H * d, OVQA_ERR_BAD_ARG,
+               "attention_decode_split: row stride smaller than H*d");
+  OVQA_REQUIRE(R * H * slices <= 0x7fffffff, OVQA_ERR_UNSUPPORTED, "attention_decode_split: R*H*slices too large");
+  ovqa::AttnDecodeArgs a{q, k, v, ldq, ldk, ldv, kv_batch_stride, mask, ldmask, o, ldo,
+                         (int)R, (int)H, (int)d, (int)n, (int)group, scale};
+  OVQA_REQUIRE(ovqa::attention_decode_supported(a, dtype == OVQA_BF16 ? 2 : 4), OVQA_ERR_UNSUPPORTED,
+               "attention_decode_split: d must be 32 / 64 / 128, 16-byte aligned q / k / v / o rows");
+  const int64_t need = ovqa::decode_split_workspace_bytes(R, H, n, d, splits);
+  OVQA_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need, OVQA_ERR_BAD_ARG,
+               "attention_decode_split: workspace NULL, not 16-byte aligned or smaller than %lld bytes", (long long)need);
+  g_dispatch = "decode-split";
+  return ovqa::attention_decode_split(dtype, a, (int)chunk, (int)slices, (float*)workspace, as_stream(stream));
+}
+
 int ovqa_decode_embed(int out_dtype, const int64_t* tokens, const float* emb, int64_t ld_emb, int64_t vocab,
                       const float* pos, int64_t ld_pos, int64_t n_pos, int64_t* seq, int64_t pad_idx, float mask_value,
                       float* mask, int64_t ld_mask, int64_t col, float* x32, void* x, int64_t R, int64_t D, void* stream) {

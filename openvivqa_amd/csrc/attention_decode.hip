@@ -20,6 +20,12 @@ namespace {
 constexpr int LMAX_KEYS = 512;  // keys of ONE window: a wave's scores for one query live in a fixed LDS slot (512 floats,
                                 // 128 per wave in the split form); longer key lists are walked window by window
 constexpr int MAX_KEYS = 1 << 30;  // key indices (and a window's end, j + 16 * 4 passes) are 32-bit ints
+constexpr int DECODE_MAX_SPLITS = 32;  // slices of the key split across workgroups (a merge lane per slice; 2048 keys / 64)
+// the automatic rule's constants (MEASURED at H = 8, d = 64, bf16, B in 1 .. 32: DESIGN section 18)
+constexpr int AUTO_MIN_SLICE = 128;   // keys of a slice: shorter slices bought nothing (the split form's floor is two launches)
+constexpr int AUTO_MAX_SPLITS = 16;   // 32 slices were slower than 16 in every cell
+constexpr int AUTO_MIN_SPLITS = 4;    // 2 slices lose at 577 / 617 keys and win under 6 % at 1024
+constexpr int AUTO_WGS_PER_CU = 1;    // workgroups per CU the split may reach: at 2 per CU, 128 problems of one query lost
 
 template <typename T> struct Vec16;  // 16 bytes of T
 template <> struct Vec16<bf16> { typedef bf16x8 type; static constexpr int N = 8; };
@@ -43,26 +49,34 @@ template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4
 // window.  WIN is a separate instantiation so that the one-window form keeps its registers and its arithmetic.
 // G = 5 .. 8 exist in the SPLIT form only (LDS: 4 waves x 8 queries x 128 floats = 16 KiB) and keep fewer loads in
 // flight per lane (UK, UV below: batching of loads, not the order of any sum).
-template <typename T, int D, int G, bool SPLIT, bool WIN>
-__global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a) {
+//
+// The body is one function for two kernels.  attn_decode_kernel hands it all keys, [0, n), and gets o stored.
+// attn_decode_part_kernel (PART = true, the SPLIT forms only) hands workgroup (problem, slice s) the keys [k_lo, k_hi) of
+// slice s: the four waves take a quarter of the SLICE each and merge through LDS as above, and instead of dividing and
+// storing o the workgroup writes its merged (M, S, unnormalised o[D]) as fp32 into record (row, head, s) of `ws` (layout at
+// decode_split_workspace_bytes); attn_decode_merge_kernel, the next launch in the stream, merges the records.
+template <typename T, int D, int G, bool SPLIT, bool WIN, bool PART>
+__device__ __forceinline__ void attn_decode_body(const ovqa::AttnDecodeArgs& a, const int wg, const int k_lo, const int k_hi,
+                                                 float* __restrict__ ws, const int slices, const int slice) {
   static_assert(G <= 4 || SPLIT, "more than 4 queries per wave: split form only");
   static_assert(!WIN || SPLIT, "past one window the four waves always share the problem");
   static_assert(!WIN || G <= 6, "windowed forms of 7 and 8 queries measured slower than the forms they would replace");
+  static_assert(!PART || SPLIT, "a partial is what the four waves of a workgroup merged");
   constexpr int SLOT = SPLIT ? LMAX_KEYS / 4 : LMAX_KEYS;  // scores a wave keeps per query
   __shared__ float sc[4][G][SLOT];
   __shared__ float red_m[4][G], red_s[4][G];
   __shared__ float red_o[SPLIT ? 4 : 1][G][D];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wid = SPLIT ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
+  const int wid = SPLIT ? wg : wg * 4 + wave;
   const int rows_g = a.R / G;
   const bool live = wid < rows_g * a.H;
   if (!SPLIT && !live) return;  // (whole waves; the non-split form has no workgroup barrier)
   const int rg = live ? wid / a.H : 0, h = live ? wid - rg * a.H : 0;
   const int r0 = rg * G;  // first query row
   // this wave's keys [j_lo, j_hi): everything, or a quarter rounded up to whole 16-key passes
-  const int quarter = ((a.n + 3) / 4 + 15) & ~15;
-  const int j_lo = SPLIT ? min(wave * quarter, a.n) : 0;
-  const int j_hi = SPLIT ? min(j_lo + quarter, a.n) : a.n;
+  const int quarter = ((k_hi - k_lo + 3) / 4 + 15) & ~15;
+  const int j_lo = SPLIT ? min(k_lo + wave * quarter, k_hi) : k_lo;
+  const int j_hi = SPLIT ? min(j_lo + quarter, k_hi) : k_hi;
   const int64_t kvrow = (int64_t)(r0 / a.group) * a.kv_batch_stride;
   const T* kb = (const T*)a.k + kvrow + h * D;
   const T* vb = (const T*)a.v + kvrow + h * D;
@@ -265,8 +279,87 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a
         S = fmaf(red_s[w][g], e, S);
         o = fmaf(red_o[w][g][f], e, o);
       }
-      if (live) ((T*)a.o)[(int64_t)(r0 + g) * a.ldo + h * D + f] = from_f32<T>(o / S);
+      if constexpr (PART) {  // the slice's record: what the four waves merged to, left unnormalised
+        const int64_t rec = ((int64_t)(r0 + g) * a.H + h) * slices + slice;
+        if (live) {
+          ws[rec * D + f] = o;
+          if (f == 0) {
+            float* ms = ws + (int64_t)a.R * a.H * slices * D + 2 * rec;
+            ms[0] = M;
+            ms[1] = S;
+          }
+        }
+      } else {
+        if (live) ((T*)a.o)[(int64_t)(r0 + g) * a.ldo + h * D + f] = from_f32<T>(o / S);
+      }
     }
+  }
+}
+
+template <typename T, int D, int G, bool SPLIT, bool WIN>
+__global__ __launch_bounds__(256) void attn_decode_kernel(ovqa::AttnDecodeArgs a) {
+  attn_decode_body<T, D, G, SPLIT, WIN, false>(a, (int)blockIdx.x, 0, a.n, nullptr, 1, 0);
+}
+
+// ---- the key split ACROSS workgroups (small batches: 8 workgroups of B = 1, H = 8 leave 248 CUs idle and each wave walks
+// its keys as a chain of round trips).  Two launches, ordered by the stream and by nothing else: no counters, no flags.
+// Workgroup b of the first = (problem b / slices, slice b % slices), keys [slice * chunk, min(+ chunk, n)): never empty,
+// a multiple of 64 keys from the start (decode_split_slices).  WIN: chunk > 512, a wave's quarter of a slice exceeds its LDS slot.
+template <typename T, int D, int G, bool WIN>
+__global__ __launch_bounds__(256) void attn_decode_part_kernel(ovqa::AttnDecodeArgs a, float* __restrict__ ws, int chunk,
+                                                               int slices) {
+  const int wg = (int)blockIdx.x / slices, slice = (int)blockIdx.x - wg * slices;
+  const int k_lo = slice * chunk;
+  attn_decode_body<T, D, G, true, WIN, true>(a, wg, k_lo, min(k_lo + chunk, a.n), ws, slices, slice);
+}
+
+// One wave per (row, head): M = max of the slices' maxima, every record scaled by exp(m_s - M) -- the formulas of the
+// in-workgroup merge; a slice whose keys are all masked has a finite maximum near -1e5 and drops out by underflow -- then
+// o / S stored with the caller's row stride.  Lane s holds slice s's (m, S) (slices <= 32); for o a lane owns a 16-byte
+// chunk of a record and the wave's 64 / (D / 4) lane groups take alternate slices, 4 loads in flight per lane.  The order
+// of every sum is fixed: same bits on every run.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_decode_merge_kernel(const float* __restrict__ ws, T* __restrict__ o, int64_t ldo,
+                                                                int RH, int H, int slices) {
+  const int lane = threadIdx.x & 63, p = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= RH) return;  // (whole waves)
+  const int r = p / H, h = p - r * H;
+  const float* wo = ws + (int64_t)p * slices * D;
+  const float* wms = ws + (int64_t)RH * slices * D + (int64_t)p * slices * 2;
+  const float m = lane < slices ? wms[2 * lane] : -INFINITY;
+  const float s = lane < slices ? wms[2 * lane + 1] : 0.f;
+  const float M = wave_max(m);
+  const float e = __expf(m - M);  // exp(-inf) = 0 for the lanes past the last slice
+  const float S = wave_sum(s * e);
+  constexpr int CH = D / 4, NG = 64 / CH, U = 4;
+  const int c = lane % CH, sg = lane / CH;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int s0 = 0; s0 < slices; s0 += NG * U) {
+    f32x4 part[U];
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      part[u] = *reinterpret_cast<const f32x4*>(wo + (int64_t)min(s0 + NG * u + sg, slices - 1) * D + c * 4);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int sl = s0 + NG * u + sg;
+      const float w = __shfl(e, min(sl, slices - 1), 64);
+      if (sl < slices) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[i] = fmaf(part[u][i], w, acc[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    float v = acc[i];
+#pragma unroll
+    for (int off = CH; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+    acc[i] = v;
+  }
+  if (sg == 0) {
+    T* orow = o + (int64_t)r * ldo + h * D + c * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) orow[i] = from_f32<T>(acc[i] / S);
   }
 }
 
@@ -397,6 +490,15 @@ static int device_cus() {
   return cus;
 }
 
+static int decode_group_max() {
+  static int group_max = -1;
+  if (group_max < 0) {
+    const char* e = getenv("OVQA_DECODE_GROUP_MAX");  // (A/B: 4 = the forms before groups of 5 .. 8, 1 = no sharing)
+    group_max = e ? atoi(e) : 8;
+  }
+  return group_max;
+}
+
 template <typename T, int D>
 static int launch_decode(const AttnDecodeArgs& a, hipStream_t st) {
   static int split_min = -1;
@@ -416,11 +518,7 @@ static int launch_decode(const AttnDecodeArgs& a, hipStream_t st) {
   //   * windowed (n > 512) stop at 6: 7 and 8 queries need every VGPR plus AGPR copies at one wave per SIMD and measured
   //     no faster than per-row reads (7) and slower than two waves of 4 (8).
   // Past 8 beams, or R not a multiple of the group, every row reads for itself.  Same bits whichever form runs.
-  static int group_max = -1;
-  if (group_max < 0) {
-    const char* e = getenv("OVQA_DECODE_GROUP_MAX");  // (A/B: 4 = the forms before groups of 5 .. 8, 1 = no sharing)
-    group_max = e ? atoi(e) : 8;
-  }
+  const int group_max = decode_group_max();
   int G = 1;
   if (a.group >= 2 && a.group <= 8 && a.R % a.group == 0) {
     // the largest divisor of the group that has a form: the G rows of a wave then belong to one sample
@@ -459,6 +557,98 @@ int attention_decode(int dtype, const AttnDecodeArgs& a, hipStream_t st) {
     case 32: return launch_decode<float, 32>(a, st);
     case 64: return launch_decode<float, 64>(a, st);
     default: return launch_decode<float, 128>(a, st);
+  }
+}
+
+// ---- the key split across workgroups -------------------------------------------------------------------------------------
+// Slice plan: chunk = ceil(n / splits) rounded up to 64 keys, slices = ceil(n / chunk) <= splits; slice s = keys
+// [s * chunk, min((s + 1) * chunk, n)): none empty, every start a multiple of 64.
+int64_t decode_split_slices(int64_t n, int64_t splits, int64_t* chunk) {
+  if (n < 1 || n > MAX_KEYS || splits < 1 || splits > DECODE_MAX_SPLITS) return -1;
+  const int64_t c = ((n + splits - 1) / splits + 63) / 64 * 64;
+  if (chunk) *chunk = c;
+  return (n + c - 1) / c;
+}
+
+// Workspace: fp32, record (row r, head h, slice s) = (r * H + h) * slices + s.  The unnormalised o of every record first
+// ([R * H * slices][d]: 16-byte aligned rows for the merge's loads), then its (M, S) pair ([R * H * slices][2]).
+// splits = 0 (the automatic rule): the size of the most slices that rule can pick.
+int64_t decode_split_workspace_bytes(int64_t R, int64_t H, int64_t n, int64_t d, int64_t splits) {
+  const int64_t slices = decode_split_slices(n, splits == 0 ? DECODE_MAX_SPLITS : splits, nullptr);
+  if (slices < 1 || R < 1 || H < 1 || d < 1) return -1;
+  return (R * H * slices * (d + 2) * (int64_t)sizeof(float) + 15) / 16 * 16;
+}
+
+// Queries per wave of the part kernel: the largest divisor of the group that is at most 4 (the forms of 5 .. 8 need two
+// workgroups per CU, which is never the small-batch case), or 1: group 5 and 7 read per row, 8 runs as two waves of 4.
+static int part_group(const int64_t R, const int64_t group) {
+  if (group < 2 || group > 8 || R % group != 0) return 1;
+  for (int g = 4; g > 1; g--)
+    if (group % g == 0 && g <= decode_group_max()) return g;
+  return 1;
+}
+
+// The automatic rule.  Fixed by the code: 1 whenever the unsplit launch already fills the chip twice
+// (launch_decode's own criterion), and never more than n / 64 (the slice plan).  Measured: see the constants.
+int64_t decode_auto_splits(int64_t R, int64_t H, int64_t group, int64_t n, int64_t d, int dtype) {
+  (void)d;
+  (void)dtype;
+  if (R < 1 || H < 1 || n < 1) return 1;
+  const int64_t problems = R / part_group(R, group) * H, cus = device_cus();
+  // up to one window (512 keys) a wave of the unsplit call has ONE round trip: with beams 1 and 5 the second launch costs
+  // more than is saved; the beam-3 cells at 512 keys won 0.6 us and are left unsplit (one threshold for every beam count)
+  if (problems >= 2 * cus || n <= LMAX_KEYS) return 1;
+  int64_t s = AUTO_WGS_PER_CU * cus / problems;
+  if (s > n / AUTO_MIN_SLICE) s = n / AUTO_MIN_SLICE;
+  if (s > AUTO_MAX_SPLITS) s = AUTO_MAX_SPLITS;
+  return s < AUTO_MIN_SPLITS ? 1 : s;
+}
+
+#define OVQA_PART(WINV)                                                                                              \
+  do {                                                                                                               \
+    OVQA_NOTE_LAUNCH((attn_decode_part_kernel<T, D, G, WINV>));                                                      \
+    hipLaunchKernelGGL((attn_decode_part_kernel<T, D, G, WINV>), grid, dim3(256), 0, st, a, ws, chunk, slices);      \
+  } while (0)
+template <typename T, int D, int G>
+static void launch_part(const AttnDecodeArgs& a, float* ws, int chunk, int slices, hipStream_t st) {
+  const dim3 grid((unsigned)((int64_t)(a.R / G) * a.H * slices));
+  if (chunk > LMAX_KEYS)  // a wave's quarter of a slice exceeds its LDS slot: the windowed instantiation
+    OVQA_PART(true);
+  else
+    OVQA_PART(false);
+}
+#undef OVQA_PART
+
+template <typename T, int D>
+static int launch_split(const AttnDecodeArgs& a, float* ws, int chunk, int slices, hipStream_t st) {
+  switch (part_group(a.R, a.group)) {
+    case 2: launch_part<T, D, 2>(a, ws, chunk, slices, st); break;
+    case 3: launch_part<T, D, 3>(a, ws, chunk, slices, st); break;
+    case 4: launch_part<T, D, 4>(a, ws, chunk, slices, st); break;
+    default: launch_part<T, D, 1>(a, ws, chunk, slices, st);
+  }
+  int rc = ovqa_check_launch("attention_decode_split (partials)");
+  if (rc != OVQA_OK) return rc;
+  const int RH = a.R * a.H;
+  OVQA_NOTE_LAUNCH((attn_decode_merge_kernel<T, D>));
+  hipLaunchKernelGGL((attn_decode_merge_kernel<T, D>), dim3((unsigned)((RH + 3) / 4)), dim3(256), 0, st,
+                     (const float*)ws, (T*)a.o, a.ldo, RH, a.H, slices);
+  return ovqa_check_launch("attention_decode_split (merge)");
+}
+
+int attention_decode_split(int dtype, const AttnDecodeArgs& a, int chunk, int slices, float* ws, hipStream_t st) {
+  if (a.R == 0 || a.H == 0) return OVQA_OK;
+  if (dtype == OVQA_BF16) {
+    switch (a.d) {
+      case 32: return launch_split<bf16, 32>(a, ws, chunk, slices, st);
+      case 64: return launch_split<bf16, 64>(a, ws, chunk, slices, st);
+      default: return launch_split<bf16, 128>(a, ws, chunk, slices, st);
+    }
+  }
+  switch (a.d) {
+    case 32: return launch_split<float, 32>(a, ws, chunk, slices, st);
+    case 64: return launch_split<float, 64>(a, ws, chunk, slices, st);
+    default: return launch_split<float, 128>(a, ws, chunk, slices, st);
   }
 }
 

@@ -75,6 +75,12 @@ struct AttnDecodeArgs {
 int topk_rows(const float* x, int64_t ldx, int64_t R, int64_t V, int k, float* vals, int64_t* idx, hipStream_t st);
 bool attention_decode_supported(const AttnDecodeArgs& a, int esize);
 int attention_decode(int dtype, const AttnDecodeArgs& a, hipStream_t st);
+// the key split across workgroups: the slice plan (-1: n or splits out of range), its fp32 workspace, the automatic
+// rule, and the two launches (partials of `slices` slices of `chunk` keys into ws, then the merge into a.o)
+int64_t decode_split_slices(int64_t n, int64_t splits, int64_t* chunk);
+int64_t decode_split_workspace_bytes(int64_t R, int64_t H, int64_t n, int64_t d, int64_t splits);
+int64_t decode_auto_splits(int64_t R, int64_t H, int64_t group, int64_t n, int64_t d, int dtype);
+int attention_decode_split(int dtype, const AttnDecodeArgs& a, int chunk, int slices, float* ws, hipStream_t st);
 
 // ---- decode_glue.hip: the index / elementwise work around a decoding step ---------------
 struct BeamCommitArgs {

@@ -9,6 +9,8 @@ projection with bias+dropout+residual epilogue -> LayerNorm.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 
@@ -379,6 +381,16 @@ class MultiHeadAttention(Module):
         return self._aoa(arena, queries, out)
 
     @staticmethod
+    def _wg_split():
+        """Keyword arguments of ``ops.attention_decode`` for OVQA_DECODE_WG_SPLIT (read per call): unset or 0 = none (the
+        unsplit call), ``auto`` = the library's rule (splits = 0), an integer N = up to N slices of the keys across
+        workgroups."""
+        v = os.environ.get("OVQA_DECODE_WG_SPLIT", "0").strip().lower()
+        if v in ("", "0"):
+            return {}
+        return {"splits": 0 if v == "auto" else int(v)}
+
+    @staticmethod
     def _row_mask(mask, R, n):
         """(R, >= n) fp32 rows of an additive (R | 1, 1, 1, n) mask, or None."""
         if mask is None:
@@ -418,7 +430,8 @@ class MultiHeadAttention(Module):
                 ops.linear_fwd_split3(x, w3, b3, (q, kc[:, n], vc[:, n]))
                 n += 1
                 self._buffers["running_keys"], self._buffers["running_values"] = kc[:, :n], vc[:, :n]
-                o = ops.attention_decode(q.view(x.shape[0], 1, -1), kc, vc, n, a.h, mask=self._row_mask(mask, x.shape[0], n))
+                o = ops.attention_decode(q.view(x.shape[0], 1, -1), kc, vc, n, a.h, mask=self._row_mask(mask, x.shape[0], n),
+                                         **self._wg_split())
                 return self._finish_step(arena, queries, o)
         q = ops.linear_fwd(queries.contiguous(), arena.compute(a.fc_q.weight), arena.master_of(a.fc_q.bias))
         if not single:  # several new positions at once (teacher-forced prefixes): the general kernel on a grown cache
@@ -436,7 +449,7 @@ class MultiHeadAttention(Module):
                        out=vc[:, n])
         n += 1
         self._buffers["running_keys"], self._buffers["running_values"] = kc[:, :n], vc[:, :n]
-        o = ops.attention_decode(q, kc, vc, n, a.h, mask=self._row_mask(mask, q.shape[0], n))
+        o = ops.attention_decode(q, kc, vc, n, a.h, mask=self._row_mask(mask, q.shape[0], n), **self._wg_split())
         return self._finish_step(arena, queries, o)
 
     def _encoder_step(self, arena, queries, keys, mask, group=1):
@@ -459,5 +472,6 @@ class MultiHeadAttention(Module):
             kv = ops.linear_fwd(keys.to(q.dtype).contiguous(), arena.packed([a.fc_k.weight, a.fc_v.weight]),
                                 arena.packed([a.fc_k.bias, a.fc_v.bias], "master"))
             self._enc = (ident, kv)
-        o = ops.attention_decode(q, kv[..., :F], kv[..., F:], nk, a.h, mask=self._row_mask(mask, R, nk), group=group)
+        o = ops.attention_decode(q, kv[..., :F], kv[..., F:], nk, a.h, mask=self._row_mask(mask, R, nk), group=group,
+                                 **self._wg_split())
         return self._finish_step(arena, queries, o)

@@ -824,10 +824,27 @@ def attention_q_fwd(x, w, bias, k, v, mask, H, scale=None, save_lse=True, lo_out
     return q, o, lse
 
 
-def attention_decode(q, k_cache, v_cache, n, H, mask=None, group=1, scale=None, out=None):
+def decode_split_slices(n, splits):
+    """Slices the key split across workgroups cuts ``n`` keys into for ``splits`` in 1 .. 32
+    (``ovqa_attention_decode_split_slices``): ceil(n / chunk), chunk = ceil(n / splits) rounded up to 64 keys."""
+    return int(_lib.load().ovqa_attention_decode_split_slices(n, splits))
+
+
+def decode_split_workspace_bytes(R, H, n, d, splits):
+    """Bytes of workspace ``attention_decode(..., splits=splits)`` needs (``ovqa_attention_decode_split_workspace_bytes``);
+    splits = 0: enough for whatever the automatic rule picks."""
+    return int(_lib.load().ovqa_attention_decode_split_workspace_bytes(R, H, n, d, splits))
+
+
+def attention_decode(q, k_cache, v_cache, n, H, mask=None, group=1, scale=None, out=None, splits=1, workspace=None):
     """One decoding step's attention (``ovqa_attention_decode``): q [R, 1, H*d] or [R, H*d]; k_cache / v_cache
     [R // group, Lmax, H*d] in-place caches of which the first ``n`` keys are live (the ``group`` beams of a sample
-    share a cache row); mask: additive fp32 [R, >= n] or None.  Returns o with q's shape."""
+    share a cache row); mask: additive fp32 [R, >= n] or None.  Returns o with q's shape.
+
+    ``splits`` != 1: the keys split across workgroups (``ovqa_attention_decode_split``: small batches, long key lists),
+    up to ``splits`` slices in 2 .. 32, or 0 = the library's automatic rule.  ``workspace``: a contiguous device tensor of
+    at least ``decode_split_workspace_bytes(R, H, n, d, splits)`` bytes; allocated here when None (under graph capture:
+    from the capture's pool)."""
     _dev(q)
     lib = _lib.load()
     shape = q.shape
@@ -843,10 +860,22 @@ def attention_decode(q, k_cache, v_cache, n, H, mask=None, group=1, scale=None, 
         assert mask.dtype == torch.float32 and mask.dim() == 2 and mask.shape[0] == R and mask.shape[1] >= n
         assert mask.stride(1) == 1
     scale = (1.0 / math.sqrt(d)) if scale is None else scale
-    _lib.check(lib.ovqa_attention_decode(_dt(q), _p(q), ldq, _p(k_cache), k_cache.stride(1), _p(v_cache),
-                                         v_cache.stride(1), k_cache.stride(0), group, _p(mask),
-                                         0 if mask is None else mask.stride(0), _p(o), o.stride(0), R, H, n, d,
-                                         float(scale), _stream()), "attention_decode")
+    if splits == 1:
+        _lib.check(lib.ovqa_attention_decode(_dt(q), _p(q), ldq, _p(k_cache), k_cache.stride(1), _p(v_cache),
+                                             v_cache.stride(1), k_cache.stride(0), group, _p(mask),
+                                             0 if mask is None else mask.stride(0), _p(o), o.stride(0), R, H, n, d,
+                                             float(scale), _stream()), "attention_decode")
+        return o
+    if workspace is None:
+        workspace = torch.empty(max(16, decode_split_workspace_bytes(R, H, n, d, splits)), dtype=torch.uint8,
+                                device=q.device)
+    assert workspace.is_cuda and workspace.is_contiguous()
+    _lib.check(lib.ovqa_attention_decode_split(_dt(q), _p(q), ldq, _p(k_cache), k_cache.stride(1), _p(v_cache),
+                                               v_cache.stride(1), k_cache.stride(0), group, _p(mask),
+                                               0 if mask is None else mask.stride(0), _p(o), o.stride(0), R, H, n, d,
+                                               float(scale), splits, _p(workspace),
+                                               workspace.numel() * workspace.element_size(), _stream()),
+               "attention_decode_split")
     return o
 
 

@@ -11,6 +11,9 @@
              ``--positions`` encoder positions (617 = 577 ViT patches + 40 question tokens), B = 64, beams 1, 3 and 5, the
              whole decode replayed from one hipGraph: tokens/s and ms per decode.
 
+``--splits 1 auto 8 --rounds 3``: the key split across workgroups (``ovqa_attention_decode_split``) against the unsplit call,
+both in this build, alternated round by round in one process; a row per value with the range of its rounds' medians.
+
 ``--tree DIR`` imports the package from another checkout (with its own built library), e.g. the parent commit, so that
 both sides of a comparison are measured by the same script, alternated on one box.  One JSON line per row.
   python scripts/long_decode_bench.py --kernel [--out profiles/r09_long_decode_bench.jsonl]
@@ -39,6 +42,9 @@ def emit(row, out):
 
 
 def kernel_row(ops, n, B, beam, H, d, a):
+    """One row per value of ``--splits``.  Several values are ALTERNATED in this process: every round times each value's
+    graph in turn (``--reps`` windows, their median), ``--rounds`` rounds; a row reports the median of its rounds' medians
+    and their range, the spread a difference between two values has to beat."""
     dev, F = "cuda", H * d
     g = torch.Generator(device=dev).manual_seed(0)
     R = B * beam
@@ -49,38 +55,65 @@ def kernel_row(ops, n, B, beam, H, d, a):
     mask = torch.zeros(R, n, device=dev)
     mask[:, n - n // 8:] = -1e5
     out = torch.empty_like(q)
+    graphs, info = [], []
+    for sp in a.splits:
+        kw, row = {}, {}
+        if sp != "1":  # (splits = 1 is the call without the keyword: a tree from before the split can run it)
+            splits = 0 if sp == "auto" else int(sp)
+            kw = {"splits": splits, "workspace": torch.empty(max(16, ops.decode_split_workspace_bytes(R, H, n, d, splits)),
+                                                             dtype=torch.uint8, device=dev)}
+            if splits == 0:
+                from openvivqa_amd import _lib
+                splits = int(_lib.load().ovqa_attention_decode_auto_splits(R, H, group, n, d, 1))
+            row = {"splits": sp, "splits_used": splits, "slices": ops.decode_split_slices(n, splits)}
+        elif len(a.splits) > 1:
+            row = {"splits": "1", "splits_used": 1, "slices": 1}
 
-    def calls():
-        for i in range(a.calls):
-            k, v = sets[i % a.sets]
-            ops.attention_decode(q, k, v, n, H, mask=mask, group=group, out=out)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        calls()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        calls()
-    for _ in range(a.warmup):
-        graph.replay()
-    torch.cuda.synchronize()
-    us = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            graph.replay()
-        e1.record()
+        def calls(kw=kw):
+            for i in range(a.calls):
+                k, v = sets[i % a.sets]
+                ops.attention_decode(q, k, v, n, H, mask=mask, group=group, out=out, **kw)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            calls()
+        torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        us.append(e0.elapsed_time(e1) * 1e3 / (a.iters * a.calls))
-    us.sort()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            calls()
+        for _ in range(a.warmup):
+            graph.replay()
+        torch.cuda.synchronize()
+        graphs.append(graph)
+        info.append(row)
+    rounds = [[] for _ in a.splits]
+    for _ in range(a.rounds):
+        for i, graph in enumerate(graphs):
+            us = []
+            for _ in range(a.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                us.append(e0.elapsed_time(e1) * 1e3 / (a.iters * a.calls))
+            us.sort()
+            rounds[i].append(us)
     kv_bytes = B * n * F * 2 * 2  # K and V of every sample once, bf16
     nbytes = kv_bytes + R * n * 4
-    med = us[len(us) // 2]
-    return {"us_per_launch": round(med, 2), "us_min": round(us[0], 2), "us_max": round(us[-1], 2),
-            "bytes": nbytes, "frac_of_hbm_peak": round(nbytes / (med * 1e-6) / PEAK_HBM, 4)}
+    rows = []
+    for row, rs in zip(info, rounds):
+        meds = sorted(us[len(us) // 2] for us in rs)
+        med = statistics.median(meds)
+        row.update({"us_per_launch": round(med, 2), "us_min": round(min(us[0] for us in rs), 2),
+                    "us_max": round(max(us[-1] for us in rs), 2), "bytes": nbytes,
+                    "frac_of_hbm_peak": round(nbytes / (med * 1e-6) / PEAK_HBM, 4)})
+        if a.rounds > 1:
+            row.update({"rounds": a.rounds, "round_medians_us": [round(m, 2) for m in meds]})
+        rows.append(row)
+    return rows
 
 
 def run_kernel(a):
@@ -88,13 +121,14 @@ def run_kernel(a):
     for n in (a.n or KERNEL_N):
         for B in (a.batch or KERNEL_B):
             for beam in (a.beam or BEAMS):
-                row = {"mode": "kernel", "tag": a.tag, "n": n, "B": B, "beam": beam, "H": 8, "d": 64, "dtype": "bf16",
-                       "ungrouped": bool(a.ungrouped)}
+                base = {"mode": "kernel", "tag": a.tag, "n": n, "B": B, "beam": beam, "H": 8, "d": 64, "dtype": "bf16",
+                        "ungrouped": bool(a.ungrouped)}
                 try:
-                    row.update(kernel_row(ops, n, B, beam, 8, 64, a))
+                    rows = kernel_row(ops, n, B, beam, 8, 64, a)
                 except RuntimeError as exc:  # (a library that refuses the shape: the row says so)
-                    row["error"] = str(exc)[:160]
-                emit(row, a.out)
+                    rows = [{"error": str(exc)[:160]}]
+                for row in rows:
+                    emit(dict(base, **row), a.out)
 
 
 def run_decoder(a):
@@ -161,6 +195,10 @@ def main():
     ap.add_argument("--beam", type=int, nargs="*")
     ap.add_argument("--ungrouped", action="store_true",
                     help="--kernel: group = 1 on caches gathered per beam (the route of a group without a shared form)")
+    ap.add_argument("--splits", nargs="*", default=["1"],
+                    help="--kernel: 1 (the unsplit call), auto (the library's rule) or N slices of the keys across "
+                         "workgroups; several values are alternated in one process")
+    ap.add_argument("--rounds", type=int, default=1, help="--kernel: alternated rounds per value of --splits")
     ap.add_argument("--calls", type=int, default=16)
     ap.add_argument("--sets", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=3)
